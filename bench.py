@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — frames/s of EndoDAV's per-clip forward on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--T 8] [--encoder vits] [--train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--T 8] [--encoder vits] [--train] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs with --dump-outputs, and prints the line.  What is
+measured beside `value` -- other_products, the three roofline objects, cpu_baseline, one_clip_at_a_time_value, pcie_inclusive_value,
+output_finite, and --train's loss_share -- is measured only with --full (null otherwise); the kernel-event brackets of the roofline steps are
+then inside the timed region, as they always were.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy in float32:
+the four disparity maps disp_0 .. disp_3 (--train: also the loss and the flat gradient buffer); the inputs are the same in every run with the
+same arguments.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its N ranks itself (self_launch: a torch.distributed.run child, before
 any GPU call here); under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.
@@ -61,6 +68,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense, MI355X_MICROARCH.md (never the 2:1-spar
 PEAK_F32_MFMA_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 PEAK_HBM_GBS = 8000.0         # same guide, "HBM3E peak BW" (spec; 6.29 TB/s measured with a float4 copy)
 PROFILE_ROUND = "r03"         # profiles/<round>_{gemm,attn,hbm}_traffic.json hold the PMC traffic of this round's kernels
+DUMP_BUDGET = 63_000_000      # bytes of array data --dump-outputs writes at most (under 64 MB with the .npy headers)
 
 
 def parse():
@@ -82,7 +90,11 @@ def parse():
     ap.add_argument("--products", default=None, choices=["f32", "bf16x6"], help="arithmetic of the encoder's linears and attention in inference (model.products; "
                     "default: the model's, bf16x6 since round 3): bf16x6 = fp32 tensors and accumulation, each product as six bf16 MFMAs on three-term bf16 "
                     "splits of both operands (error no worse than the fp32 pipe's: tests/test_gemm_x6_gpu.py, tests/test_attn_x6_gpu.py); f32 = fp32 products "
-                    "on the fp32 matrix pipe everywhere.  The other mode is always timed beside `value` (other_products)")
+                    "on the fp32 matrix pipe everywhere.  With --full the other mode is timed beside `value` (other_products)")
+    ap.add_argument("--full", action="store_true", help="also measure what is reported beside `value`: kernel rooflines (HIP event brackets in the first "
+                    "timed steps), the one-clip-at-a-time and other-products legs, the PCIe-inclusive variant and the CPU baseline; off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32; a fixed, "
+                    "seeded sample of each array if they exceed 64 MB in all)")
     ap.add_argument("--no-other-products", action="store_true", help="skip the leg that times the other products mode (profiling passes: one arithmetic per run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events")
@@ -205,6 +217,23 @@ def hbm_roofline(model, encoder, T, image_hw, clips):
                     "groupnorm = statistics + apply launches of one call"}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32.  Above DUMP_BUDGET bytes in all, every array is cut to its share of the budget
+    by a sample of flat indices (sorted) that depends only on the array's size, so two runs of the same arguments sample the same elements."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if total > DUMP_BUDGET:
+            k = max(1, a.numel() * DUMP_BUDGET // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.numel(), size=k, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: start the N ranks ourselves -- one child running
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <the same arguments>`
@@ -289,7 +318,7 @@ def main():
 
     if args.train:
         return train_bench(args, model, x, dev, rank, world, kwargs, rehearsal)
-    events = not args.no_kernel_events
+    events = args.full and not args.no_kernel_events
     with torch.no_grad():
         model(x)  # creates the context (profile_* need one)
         if events:
@@ -330,8 +359,10 @@ def main():
             model.set_encoder_streams(-1)
         if handles:
             out["maps"] = handles[-1].result()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {f"disp_{s}": out["maps"][("disp", s)] for s in range(4)})
         serial_value = None
-        if flight is not None:  # the same steps one clip at a time (reported beside `value`, never as it)
+        if flight is not None and args.full:  # the same steps one clip at a time (reported beside `value`, never as it)
             n_s = max(args.steps // 2, 4)
             torch.cuda.synchronize(dev)
             t1 = time.perf_counter()
@@ -342,7 +373,7 @@ def main():
         # The other products mode on the same clip, same clips in flight (reported beside `value`, never as it): how much the bf16 x 6 linears buy at
         # this shape, and how far the two modes' disparities are apart.
         other = None
-        if world == 1 and not stub_alt(args):
+        if world == 1 and args.full and not stub_alt(args):
             first = model.products
             model.products = "bf16x6" if first == "f32" else "f32"
             n_o = max(args.steps // 2, 4)
@@ -440,7 +471,7 @@ def main():
     # PCIe-inclusive variant (never `value`): pinned host clip -> HBM on a copy stream while the previous clip computes, forward, the four
     # maps -> pinned host memory on a second copy stream (endodav_amd/pipeline.py); the reference does both transfers synchronously
     pcie_value = None
-    if world == 1:
+    if world == 1 and args.full:
         model.profile_enable([])
         pipe = ClipPipeline(model, dev)
         xh = x.cpu().pin_memory()
@@ -452,7 +483,7 @@ def main():
         taken = sum(1 for _ in pipe.run(xh for _ in range(n_p)))
         torch.cuda.synchronize(dev)
         pcie_value = Bc * T * taken / (time.perf_counter() - t1)
-    finite = bool(torch.isfinite(out[("disp", 0)]).all().item())
+    finite = bool(torch.isfinite(out[("disp", 0)]).all().item()) if args.full else None
     if rank == 0:
         frames = world * Bc * T * args.steps
         value = frames / dt
@@ -476,7 +507,7 @@ def main():
             "other_products": other,
             "roofline": roofline, "roofline_attention": roofline_attn, "roofline_hbm": roofline_hbm,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(kwargs, T, (SH, SW), args.cpu_threads)
         else:
             line["cpu_baseline"] = None
@@ -522,7 +553,7 @@ def train_bench(args, model, x, dev, rank, world, kwargs, rehearsal=False):
             inp[k].requires_grad_(True)
     side_leaves = [v for v in inp.values() if v.requires_grad]
     wts = losses.TrainerLossWeights(depth_reproj=1e-2, depth_flow=1e-3, tune_temporal=True) if args.depth_consistency else losses.TrainerLossWeights()
-    events = not args.no_kernel_events
+    events = args.full and not args.no_kernel_events
     lin_from = args.steps - min(LIN_STEPS, args.steps)
     state = {}
 
@@ -553,10 +584,18 @@ def train_bench(args, model, x, dev, rank, world, kwargs, rehearsal=False):
         state["n"] = parallel.allreduce_gradients(params, model=model)
         opt.step()
         state["loss"] = loss
+        if i == args.steps - 1:
+            state["maps"] = out
 
     model(x)  # creates the context
     model.profile_enable([])
     dt, _ = parallel.timed_region(step, args.steps, max(args.warmup, 1), dev)
+    if args.dump_outputs and rank == 0:
+        arrays = {f"disp_{s}": state["maps"][("disp", s)] for s in range(4)}
+        arrays["loss"] = state["loss"]
+        flat = model.flat_gradients(params)
+        arrays["gradients"] = flat if flat is not None else torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None])
+        dump_outputs(args.dump_outputs, arrays)
     roofline = loss_share = roofline_hbm = None
     roofline_attn = {}
     if events:

@@ -15,10 +15,10 @@ ONLY=${EVIDENCE_ONLY:-all}   # "mfma": only the MFMA-busy pass; "pmc": the three
 mkdir -p $O
 cd $R
 if [ "$ONLY" = "all" ]; then
-timeout -k 10 500 python bench.py "$@" > $O/$name.json 2> $O/$name.err || echo "bench $name failed" >> $O/fail.log
+timeout -k 10 500 python bench.py --full "$@" > $O/$name.json 2> $O/$name.err || echo "bench $name failed" >> $O/fail.log
 echo "bench $name: $(head -c 160 $O/$name.json)"
 fi
-PROF="--no-cpu-baseline --no-kernel-events --no-other-products --steps 4 --warmup 2"
+PROF="--full --no-cpu-baseline --no-kernel-events --no-other-products --steps 4 --warmup 2"
 case " $* " in *" --train "*) ;; *) PROF="$PROF --in-flight 1";; esac
 [ "$ONLY" != "all" ] || (cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -o k -- python3 $R/bench.py "$@" $PROF > $O/prof_$name.log 2>&1) || echo "rocprof $name failed" >> $O/fail.log
 f=$(find $O/prof_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv

@@ -8,8 +8,8 @@ mkdir -p $O
 cd $R
 run() { # name, bench args...
   name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $O/$name.json 2> $O/$name.err || echo "bench $name failed" >> $O/fail.log
-  (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -o k -- python3 $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 "$@" > $O/prof_$name.log 2>&1) || echo "rocprof $name failed" >> $O/fail.log
+  timeout -k 10 400 python bench.py --full "$@" > $O/$name.json 2> $O/$name.err || echo "bench $name failed" >> $O/fail.log
+  (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -o k -- python3 $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 "$@" > $O/prof_$name.log 2>&1) || echo "rocprof $name failed" >> $O/fail.log
   f=$(find $O/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv
   rm -rf $O/prof_$name

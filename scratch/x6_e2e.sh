@@ -5,7 +5,7 @@ for cfg in "vits 8 20 5" "vitb 16 8 2" "vitl 32 4 1"; do
   set -- $cfg
   for m in "f32 1" "bf16x6 0" "bf16x6 1"; do
     set -- $cfg $m
-    EDV_X6_ATTN=$6 python bench.py --encoder $1 --T $2 --steps $3 --warmup $4 --products $5 --no-cpu-baseline --no-kernel-events --no-other-products > /tmp/ab.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; continue; }
+    EDV_X6_ATTN=$6 python bench.py --encoder $1 --T $2 --steps $3 --warmup $4 --products $5 --full --no-cpu-baseline --no-kernel-events --no-other-products > /tmp/ab.json 2>/tmp/ab.err || { tail -3 /tmp/ab.err; continue; }
     python - <<PY
 import json
 j=json.load(open("/tmp/ab.json"))

@@ -73,8 +73,8 @@ def _grad_worker(rank, world, port, q):
     if rank == 0:
         ps[2].grad = torch.tensor([3.0, 6.0, 9.0])
     n = parallel.allreduce_gradients(ps + [frozen])
-    if rank == 0:
-        q.put((n, [p.grad.clone() for p in ps], frozen.grad))
+    if rank == 0:  # numpy arrays travel by value; a tensor would travel as a file descriptor that dies with this process
+        q.put((n, [p.grad.numpy().copy() for p in ps], frozen.grad))
     parallel.barrier()
     dist.destroy_process_group()
 
@@ -88,6 +88,7 @@ def test_gradient_allreduce_gloo():
     for p in procs:
         p.start()
     n, grads, frozen_grad = q.get(timeout=120)
+    grads = [torch.from_numpy(g) for g in grads]
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -163,7 +164,7 @@ def _r2_worker(rank, world, port, q):
 
     n = parallel.allreduce_gradients(ps, model=M())
     if rank == 0:
-        q.put(dict(dt=dt, last=last, seen=seen, res=res, out=out, calls=runner.calls, n=n, flat=flat.clone(), g0=ps[0].grad.clone()))
+        q.put(dict(dt=dt, last=last, seen=seen, res=res, out=out, calls=runner.calls, n=n, flat=flat.numpy().copy(), g0=ps[0].grad.numpy().copy()))
     else:
         assert res is None and out is None
     parallel.barrier()
@@ -198,8 +199,8 @@ def test_round2_sharded_paths_equal_the_one_rank_run():
     assert solo.shape == (95, 12, 16) and np.array_equal(got["out"], solo)
     assert got["calls"] == [10, 54, 94]  # rank 0 ran windows 0, 2, 4 (original frame shown in slot 10; 98 is padding -> the last frame)
     # (4)
-    assert got["n"] == 12 and torch.equal(got["flat"], torch.arange(12, dtype=torch.float32) * 1.5)
-    assert torch.equal(got["g0"], (torch.arange(8, dtype=torch.float32) * 1.5).view(2, 4))  # .grad is a view: reduced in place
+    assert got["n"] == 12 and torch.equal(torch.from_numpy(got["flat"]), torch.arange(12, dtype=torch.float32) * 1.5)
+    assert torch.equal(torch.from_numpy(got["g0"]), (torch.arange(8, dtype=torch.float32) * 1.5).view(2, 4))  # .grad is a view: reduced in place
 
 
 class _VideoDepther:
