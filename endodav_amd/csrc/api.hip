@@ -1,5 +1,7 @@
 // extern "C" per-kernel entry points declared in include/endodav_hip.h (unit tests, micro-benchmarks).
 #include "../../include/endodav_hip.h"
+#include <vector>
+
 #include "ops.hpp"
 
 using namespace edv;
@@ -149,6 +151,24 @@ size_t edv_colsum_workspace(int32_t N) { return colsum_workspace(N) * sizeof(flo
 int edv_colsum_rows(const float *P_dev, const float *rowscale_dev, int64_t M, int32_t N, float *workspace_dev, size_t workspace_bytes, float *out_dev,
                     int32_t accumulate, void *stream) {
     return colsum_rows(P_dev, rowscale_dev, M, N, workspace_dev, workspace_bytes / sizeof(float), out_dev, accumulate != 0, (hipStream_t)stream);
+}
+size_t edv_colsum_batch_workspace(int32_t n, const int64_t *rows, const int32_t *cols) {
+    std::vector<long long> r(rows, rows + n);
+    std::vector<int> c(cols, cols + n);
+    return colsum_batch_workspace(n, r.data(), c.data()) * sizeof(float);
+}
+int edv_colsum_batch(int32_t n, const float *const *src_dev, const int64_t *ld, const int64_t *rows, const int32_t *row_map, const int32_t *cols,
+                     const float *const *scale_dev, float *const *dst_dev, const int32_t *accumulate, float *workspace_dev, size_t workspace_bytes, void *stream) {
+    EDV_CHECK(n >= 0 && (n == 0 || (src_dev && ld && rows && cols && dst_dev)), "null argument");
+    std::vector<long long> l(ld, ld + n), r(rows, rows + n);
+    std::vector<int> c(cols, cols + n), acc(n, 0);
+    std::vector<RowMap> maps(n, identity_map());
+    for (int k = 0; k < n; ++k) {
+        if (row_map) maps[k] = RowMap{row_map[3 * k], row_map[3 * k + 1], row_map[3 * k + 2]};
+        if (accumulate) acc[k] = accumulate[k];
+    }
+    return colsum_batch(n, src_dev, l.data(), r.data(), maps.data(), c.data(), scale_dev, dst_dev, acc.data(), workspace_dev, workspace_bytes / sizeof(float),
+                        (hipStream_t)stream);
 }
 int edv_groupnorm_bwd(const float *x_dev, const float *stats_dev, const float *w_dev, const float *dy_dev, float *sums_dev, float *dx_dev, int32_t F,
                       int32_t P, int32_t C, int32_t groups, int32_t accumulate, void *stream) {

@@ -83,6 +83,8 @@ struct edv_ctx {
     bool grad_temporal = true;    // spatial and temporal tuning phases (trainer_end_to_end_video.py:327-339)
     bool grad_res = false;        // parameters of the residual bottleneck blocks (residual_*, trainable by default in the reference)
     bool grad_head = false;       // weight / bias gradients of the output-head convolutions (conv_depth_*, or scratch.output_conv* with --train_output_conv)
+    bool grad_enc_bias = false;   // every pretrained.*bias (edv_set_bias_grads; bias="all" of endodav/layers.py:5-34)
+    bool grad_head_bias = false;  // every head.*bias the forward reaches
     std::unordered_map<std::string, Buf> grads;  // gradients of the trainable parameters, owned
     // Caller-owned flat gradient buffer (edv_grad_bind_flat): a gradient whose name is listed here is written straight into its slice
     // of that buffer instead of into `grads` -- the host's .grad tensors are views of it and the data-parallel all-reduce runs on
@@ -368,6 +370,58 @@ struct Run {
         return fold_bn(w, b, g, beta, mean, var, 1e-5f, bo, nout, K, st);
     }
 
+    // The packings that embed a bias (pack_convT replicates it s^2 times, fold_bn folds the BatchNorm into it, pack_geglu interleaves
+    // it): edv_prepare builds them, edv_refresh_lora rebuilds them, so that a changed bias reaches the next forward either way.
+    int pack_resize() {  // ConvTranspose k=s -> GEMM weights
+        const int *oc = cfg.out_channels;
+        const int ss[2] = {4, 2};
+        for (int j = 0; j < 2; ++j) {
+            const std::string p = "head.resize_layers." + std::to_string(j);
+            const float *w, *b;
+            EDV_TRY(param(p + ".weight", &w, 4));
+            EDV_TRY(param(p + ".bias", &b));
+            float *wo, *bo;
+            EDV_TRY(pk(p + ".weight", (size_t)ss[j] * ss[j] * oc[j] * oc[j], &wo));
+            EDV_TRY(pk(p + ".bias", (size_t)ss[j] * ss[j] * oc[j], &bo));
+            EDV_TRY(pack_convT(w, wo, b, bo, oc[j], oc[j], ss[j], st));
+        }
+        return 0;
+    }
+    // the ResidualConvUnits' convolutions; bn_only: just those whose packing folds a BatchNorm (and with it the conv bias)
+    int pack_rcus(bool bn_only) {
+        if (bn_only && !cfg.use_bn) return 0;
+        for (int j = 1; j <= 4; ++j)
+            for (int u = 1; u <= 2; ++u) {
+                if (j == 4 && u == 1) continue;  // refinenet4.resConfUnit1 is never reached (dpt_pyramid.py:81)
+                const std::string p = "head.scratch.refinenet" + std::to_string(j) + ".resConfUnit" + std::to_string(u);
+                EDV_TRY(pack_c3(p + ".conv1"));
+                EDV_TRY(pack_c3(p + ".conv2"));
+                if (cfg.use_bn) {
+                    EDV_TRY(fold_bn_into(p + ".conv1", p + ".bn1"));
+                    EDV_TRY(fold_bn_into(p + ".conv2", p + ".bn2"));
+                }
+            }
+        return 0;
+    }
+    int pack_geglus() {  // interleaved copy of ff.net.0.proj for the fused GEGLU launch of the inference forward
+        const int *oc = cfg.out_channels;
+        const int mmC[4] = {oc[2], oc[3], Fe, Fe};
+        for (int m = 0; m < 4; ++m) {
+            const std::string tb = "head.motion_modules." + std::to_string(m) + ".temporal_transformer.transformer_blocks.0";
+            const int C = mmC[m];
+            if ((8 * C) % 64 == 0 && C % 32 == 0) {
+                const float *w0, *b0;
+                float *wi, *bi;
+                EDV_TRY(param(tb + ".ff.net.0.proj.weight", &w0, 2));
+                EDV_TRY(param(tb + ".ff.net.0.proj.bias", &b0));
+                EDV_TRY(pk(tb + ".ff.net.0.geglu.w", (size_t)8 * C * C, &wi));
+                EDV_TRY(pk(tb + ".ff.net.0.geglu.b", (size_t)8 * C, &bi));
+                EDV_TRY(pack_geglu(w0, b0, wi, bi, 8 * C, C, st));
+            }
+        }
+        return 0;
+    }
+
     int prepare() {
         c->launches = 0;
         {   // patch-embed weight [D, 3*14*14 = 588] with its rows zero-padded to PE_K = 608 = 19 x 32: the im2col GEMM then runs on the
@@ -387,32 +441,10 @@ struct Run {
         for (int i = 0; i < depth; ++i)
             if (cfg.residual_mask & (1u << i)) EDV_TRY(pack_c3("pretrained.blocks." + std::to_string(i) + ".residual_.conv2"));
         const int *oc = cfg.out_channels;
-        {  // ConvTranspose k=s -> GEMM weights
-            const int ss[2] = {4, 2};
-            for (int j = 0; j < 2; ++j) {
-                const std::string p = "head.resize_layers." + std::to_string(j);
-                const float *w, *b;
-                EDV_TRY(param(p + ".weight", &w, 4));
-                EDV_TRY(param(p + ".bias", &b));
-                float *wo, *bo;
-                EDV_TRY(pk(p + ".weight", (size_t)ss[j] * ss[j] * oc[j] * oc[j], &wo));
-                EDV_TRY(pk(p + ".bias", (size_t)ss[j] * ss[j] * oc[j], &bo));
-                EDV_TRY(pack_convT(w, wo, b, bo, oc[j], oc[j], ss[j], st));
-            }
-        }
+        EDV_TRY(pack_resize());
         EDV_TRY(pack_c3("head.resize_layers.3"));
         for (int j = 1; j <= 4; ++j) EDV_TRY(pack_c3("head.scratch.layer" + std::to_string(j) + "_rn"));
-        for (int j = 1; j <= 4; ++j)
-            for (int u = 1; u <= 2; ++u) {
-                if (j == 4 && u == 1) continue;  // refinenet4.resConfUnit1 is never reached (dpt_pyramid.py:81)
-                const std::string p = "head.scratch.refinenet" + std::to_string(j) + ".resConfUnit" + std::to_string(u);
-                EDV_TRY(pack_c3(p + ".conv1"));
-                EDV_TRY(pack_c3(p + ".conv2"));
-                if (cfg.use_bn) {
-                    EDV_TRY(fold_bn_into(p + ".conv1", p + ".bn1"));
-                    EDV_TRY(fold_bn_into(p + ".conv2", p + ".bn2"));
-                }
-            }
+        EDV_TRY(pack_rcus(false));
         if (cfg.conv_head) {
             for (int k = 1; k <= 4; ++k) {
                 EDV_TRY(pack_c3("head.conv_depth_" + std::to_string(k) + ".head.0"));
@@ -438,16 +470,8 @@ struct Run {
                 }
             }
             EDV_TRY(fold_linear(tb + ".ff.net.2", cfg.temporal_lora != 0));
-            if ((8 * C) % 64 == 0 && C % 32 == 0) {  // interleaved copy of ff.net.0.proj for the fused GEGLU launch of the inference forward
-                const float *w0, *b0;
-                float *wi, *bi;
-                EDV_TRY(param(tb + ".ff.net.0.proj.weight", &w0, 2));
-                EDV_TRY(param(tb + ".ff.net.0.proj.bias", &b0));
-                EDV_TRY(pk(tb + ".ff.net.0.geglu.w", (size_t)8 * C * C, &wi));
-                EDV_TRY(pk(tb + ".ff.net.0.geglu.b", (size_t)8 * C, &bi));
-                EDV_TRY(pack_geglu(w0, b0, wi, bi, 8 * C, C, st));
-            }
         }
+        EDV_TRY(pack_geglus());
         c->x6.clear();
         EDV_TRY(build_x6(false));
         c->prepared = true;
@@ -498,6 +522,10 @@ struct Run {
             EDV_TRY(pack_c3(cv));
             if (c->train_prepared) EDV_TRY(make_b_c3(cv));
         }
+        // bias="all": every bias may have changed.  Most are read straight from the bound tensor; these three packings copy one.
+        EDV_TRY(pack_resize());
+        EDV_TRY(pack_rcus(true));
+        EDV_TRY(pack_geglus());
         EDV_TRY(build_x6(true));  // fc1 / fc2 carry the factors: their planes follow the fold
         return 0;
     }
@@ -831,6 +859,12 @@ struct Run {
         const float *w;
         EDV_TRY(param(norm + ".weight", &w));
         EDV_TRY(layernorm_bwd(x, identity_map(), w, dy, identity_map(), dx, identity_map(), rows, dim, 1e-6f, false, st));
+        if (!c->grad_res && c->grad_enc_bias) {  // bias="all" without the residual scope: the bias only, as the residual scope makes it
+            float *part, *db;
+            EDV_TRY(wsbuf("g.rb.part", (size_t)TALL_SPLITS * D, &part));
+            EDV_TRY(gradbuf(norm + ".bias", (size_t)dim, &db));
+            return col_dot(dy, nullptr, rows, dim, nullptr, part, db, st);
+        }
         if (!c->grad_res) return 0;
         float *ones, *zeros, *xhat, *part, *dw, *db;
         EDV_TRY(wsbuf("g.rb.ones", (size_t)D, &ones));
@@ -1413,8 +1447,8 @@ struct Run {
 
     // =========================================================================================
     // Backward.  Trainable: the LoRA / DV-LoRA factors of mlp.fc1 / mlp.fc2 in every encoder
-    // block (endodav/layers.py:5-34 names lora_A, lora_B, lora_U, lora_V); everything else is frozen, so each operator
-    // contributes its input gradient only.  Mirrors forward() in reverse on the activations a training forward kept.
+    // block (endodav/layers.py:5-34 names lora_A, lora_B, lora_U, lora_V), the scopes of edv_set_grad_scope and, under
+    // edv_set_bias_grads, the biases (bias="all"); everything else is frozen, so each operator contributes its input gradient only.  Mirrors forward() in reverse on the activations a training forward kept.
     float *lora_ws = nullptr;  // workspace of lora_grads for the whole backward
     size_t lora_ws_n = 0;
     int gradbuf(const std::string &name, size_t n, float **out) {
@@ -1434,6 +1468,76 @@ struct Run {
         *out = it->second.p;
         return 0;
     }
+    // ---- bias gradients (edv_set_bias_grads).  Stage 1 of the batched column sum (bias_colsum.hip) runs where each dY is still live --
+    // bias_flush() before a buffer that a pending job reads is overwritten -- and stage 2 runs once, in bias_finish(), for every tensor.
+    float *bias_slab = nullptr;
+    size_t bias_slab_n = 0, bias_slab_off = 0;
+    std::vector<ColsumJob> bias_jobs;  // stage 1, not launched yet
+    struct BiasOut {
+        std::string name;
+        size_t off;
+        int rows, N;
+        const float *scale;
+    };
+    std::vector<BiasOut> bias_outs;
+    struct BiasSrc {
+        const float *p;
+        long long rows;
+        int ld;
+        RowMap map;
+    };
+    // gradient of `name` = scale (.) sum of the rows of every source (all [rows, N], row stride ld)
+    int bias_grad(const std::string &name, const std::vector<BiasSrc> &srcs, int N, const float *scale = nullptr) {
+        BiasOut o{name, bias_slab_off, 0, N, scale};
+        for (const BiasSrc &sr : srcs) {
+            ColsumJob j = colsum_job(sr.p, sr.ld, sr.rows, sr.map, N);
+            EDV_CHECK(bias_slab_off + (size_t)j.parts * N <= bias_slab_n, "bias gradient slab too small for " + name);
+            j.slab = bias_slab + bias_slab_off;
+            bias_slab_off += (size_t)j.parts * N;
+            o.rows += j.parts;
+            bias_jobs.push_back(j);
+        }
+        bias_outs.push_back(o);
+        return 0;
+    }
+    int bias_grad(const std::string &name, const float *p, long long rows, int N, const float *scale = nullptr) {
+        return bias_grad(name, {BiasSrc{p, rows, N, identity_map()}}, N, scale);
+    }
+    int bias_flush() {
+        if (bias_jobs.empty()) return 0;
+        c->launches += ((int)bias_jobs.size() + CS_MAX_JOBS - 1) / CS_MAX_JOBS;
+        EDV_TRY(colsum_stage1_launch(bias_jobs.data(), (int)bias_jobs.size(), st));
+        bias_jobs.clear();
+        return 0;
+    }
+    int bias_finish() {
+        EDV_TRY(bias_flush());
+        if (bias_outs.empty()) return 0;
+        std::vector<ColsumOut> outs;
+        for (const BiasOut &o : bias_outs) {
+            float *dst;
+            EDV_TRY(gradbuf(o.name, (size_t)o.N, &dst));
+            outs.push_back(ColsumOut{bias_slab + o.off, o.rows, o.N, o.scale, dst, 0});
+        }
+        c->launches += ((int)outs.size() + CS_MAX_OUTS - 1) / CS_MAX_OUTS;
+        EDV_TRY(colsum_stage2_launch(outs.data(), (int)outs.size(), st));
+        bias_outs.clear();
+        return 0;
+    }
+    int bias_begin() {
+        bias_jobs.clear();
+        bias_outs.clear();
+        bias_slab_off = 0;
+        if (!c->grad_enc_bias && !c->grad_head_bias) return 0;
+        // every source job holds at most CS_MAX_PARTS partial rows; pretrained.norm.bias has up to eight sources (four taps, four cls rows)
+        size_t n = 8 * (size_t)D;
+        for (const auto &kv : c->params)
+            if (kv.first.size() > 5 && kv.first.compare(kv.first.size() - 5, 5, ".bias") == 0) n += kv.second.numel();
+        bias_slab_n = n * CS_MAX_PARTS;
+        return wsbuf("g.bias.slab", bias_slab_n, &bias_slab);
+    }
+    bool head_params() const { return c->grad_head || c->grad_head_bias; }
+
     // transposed (NT-form) weight of dX = (dY * gamma) W, cached under "T." + key
     int make_t(const std::string &key, const float *W, int ldw, int N, int K, const float *gamma) {
         float *wt;
@@ -1547,7 +1651,7 @@ struct Run {
     }
     // weight + bias gradient of a trainable 3x3 convolution p (x: its input, dY: the gradient of its output), when the caller asked for them
     int conv_param_grads(const std::string &p, const float *x, const float *dY, int H, int W, int Cin, int Cout) {
-        if (!c->grad_head) return 0;
+        if (!c->grad_head) return c->grad_head_bias ? bias_grad(p + ".bias", dY, (long long)F * H * W, Cout) : 0;
         float *dw, *db, *ws;
         EDV_TRY(gradbuf(p + ".weight", (size_t)Cout * Cin * 9, &dw));
         EDV_TRY(gradbuf(p + ".bias", (size_t)Cout, &db));
@@ -1562,7 +1666,7 @@ struct Run {
     }
     // weight + bias gradient of a 1x1 convolution to one channel: dW[c] = sum_p gz[p] o2[p, c], db = sum_p gz[p]
     int dot_param_grads(const std::string &p, const float *o2, const float *gz, long long npix, int C) {
-        if (!c->grad_head) return 0;
+        if (!c->grad_head) return c->grad_head_bias ? bias_grad(p + ".bias", gz, npix, 1) : 0;
         float *dw, *db, *ws;
         EDV_TRY(gradbuf(p + ".weight", (size_t)C, &dw));
         EDV_TRY(gradbuf(p + ".bias", 1, &db));
@@ -1605,10 +1709,19 @@ struct Run {
         EDV_TRY(dgemm(dh, M, C, tb + ".ff.net.2", 4 * C, t4));             // h3 = h2 + ff2 W2
         EDV_TRY(geglu_bwd(ff1, t4, t8, M, 4 * C, st));
         EDV_TRY(dgemm(t8, M, 8 * C, tb + ".ff.net.0.proj", C, t1));
+        const bool hb = c->grad_head_bias;
+        if (hb) {  // dh, t1 are about to change: each bias's dY while it is live
+            EDV_TRY(bias_grad(p + ".proj_out.bias", d, M, C));
+            EDV_TRY(bias_grad(tb + ".ff.net.2.bias", dh, M, C));
+            EDV_TRY(bias_grad(tb + ".ff.net.0.proj.bias", t8, M, 8 * C));
+            EDV_TRY(bias_grad(tb + ".ff_norm.bias", t1, M, C));
+            EDV_TRY(bias_flush());
+        }
         EDV_TRY(param(tb + ".ff_norm.weight", &w));
         EDV_TRY(layernorm_bwd(hsv[2], identity_map(), w, t1, identity_map(), dh, identity_map(), M, C, 1e-5f, true, st));
         for (int a = 1; a >= 0; --a) {
             const std::string ab = tb + ".attention_blocks." + std::to_string(a);
+            if (hb) EDV_TRY(bias_grad(ab + ".to_out.0.bias", dh, M, C));
             EDV_TRY(dgemm(dh, M, C, ab + ".to_out.0", C, t1));             // h(a+1) = h(a) + to_out(att)
             EDV_TRY(attn_temporal_bwd(qkvs[a], t1, t3, B, T, P, C, 8, st));  // qkvs[a] holds the rotated q|k under pe="rope"
             if (cfg.pe_rope) {
@@ -1617,10 +1730,19 @@ struct Run {
                 EDV_TRY(rope_qk(t3, rope, B, T, P, C, true, st));
             }
             EDV_TRY(dgemm(t3, M, 3 * C, ab + ".qkv", C, t1));
+            if (hb) {
+                EDV_TRY(bias_grad(tb + ".norms." + std::to_string(a) + ".bias", t1, M, C));
+                EDV_TRY(bias_flush());
+            }
             EDV_TRY(param(tb + ".norms." + std::to_string(a) + ".weight", &w));
             EDV_TRY(layernorm_bwd(hsv[a], identity_map(), w, t1, identity_map(), dh, identity_map(), M, C, 1e-5f, true, st));
         }
         EDV_TRY(dgemm(dh, M, C, p + ".proj_in", C, t1));
+        if (hb) {
+            EDV_TRY(bias_grad(p + ".proj_in.bias", dh, M, C));
+            EDV_TRY(bias_grad(p + ".norm.bias", t1, M, C));  // GroupNorm: d beta = sum of dy
+            EDV_TRY(bias_flush());
+        }
         EDV_TRY(param(p + ".norm.weight", &w));
         EDV_TRY(groupnorm_bwd(xin, stats, w, t1, sums, d, F, P, C, 32, true, st));
         c->launches += 8;
@@ -1633,19 +1755,28 @@ struct Run {
         const std::string tg = "fu" + std::to_string(j) + ".";
         const size_t n = (size_t)F * h * w * Fe;
         const long long MP_ = (long long)F * h * w;
-        float *a, *b2;
+        float *a, *b2, *a0;
         EDV_TRY(wsbuf("g.fu.a", n, &a));
         EDV_TRY(wsbuf("g.fu.b", n, &b2));
+        const bool hb = c->grad_head_bias;
+        a0 = a;
+        if (hb) EDV_TRY(wsbuf("g.fu.a0", n, &a0));  // out_conv's dY stays live until the first flush below
         const float *t1a = nullptr, *t1b, *cur = cur_or_x;
         EDV_TRY(saved(tg + "t1b", &t1b));
         if (skip) {
             EDV_TRY(saved(tg + "t1a", &t1a));
             EDV_TRY(saved(tg + "s", &cur));
         }
-        EDV_TRY(bilinear_bwd(d_out, a, F, h, w, Fe, oh, ow, false, st));                      // out = up(out_conv(t2))
-        EDV_TRY(dgemm(a, MP_, Fe, p + ".out_conv", Fe, d_x));                                  // d_x <- d_t2 for now
+        EDV_TRY(bilinear_bwd(d_out, a0, F, h, w, Fe, oh, ow, false, st));                     // out = up(out_conv(t2))
+        EDV_TRY(dgemm(a0, MP_, Fe, p + ".out_conv", Fe, d_x));                                 // d_x <- d_t2 for now
         EDV_TRY(dconv3(d_x, h, w, Fe, p + ".resConfUnit2.conv2", Fe, a));                      // t2 = cur + conv2(relu(t1b))
         EDV_TRY(ew_bwd(a, t1b, nullptr, a, (long long)n, 2, st));
+        if (hb) {  // the upsample's weights sum to one: out_conv's bias gradient is the column sum before or after it
+            EDV_TRY(bias_grad(p + ".out_conv.bias", a0, MP_, Fe));
+            EDV_TRY(bias_grad(p + ".resConfUnit2.conv2.bias", d_x, MP_, Fe));
+            EDV_TRY(bias_grad(p + ".resConfUnit2.conv1.bias", a, MP_, Fe));
+            EDV_TRY(bias_flush());
+        }
         EDV_TRY(dconv3(a, h, w, Fe, p + ".resConfUnit2.conv1", Fe, b2));                       // t1b = conv1(relu(cur))
         EDV_TRY(ew_bwd(b2, cur, d_x, d_x, (long long)n, 2, st));                               // d_cur = d_t2 + mask(cur) * .
         if (skip) {                                                                            // cur = x + skip + conv2a(relu(t1a))
@@ -1653,6 +1784,11 @@ struct Run {
             EDV_TRY(ew_bwd(a, t1a, nullptr, a, (long long)n, 2, st));
             EDV_TRY(dconv3(a, h, w, Fe, p + ".resConfUnit1.conv1", Fe, b2));                   // t1a = conv1a(relu(skip))
             EDV_TRY(ew_bwd(b2, skip, d_x, d_skip, (long long)n, 2, st));
+            if (hb) {
+                EDV_TRY(bias_grad(p + ".resConfUnit1.conv2.bias", d_x, MP_, Fe));
+                EDV_TRY(bias_grad(p + ".resConfUnit1.conv1.bias", a, MP_, Fe));
+                EDV_TRY(bias_flush());
+            }
         }
         c->launches += 6;
         return 0;
@@ -1692,6 +1828,7 @@ struct Run {
             lora_ws_n = need;
         }
 
+        EDV_TRY(bias_begin());
         float *d_p1, *d_p2, *d_p3, *d_p4, *d_r[5];
         EDV_TRY(wsbuf("g.p1", (size_t)F * h0 * w0 * Fe, &d_p1));
         EDV_TRY(wsbuf("g.p2", (size_t)F * h1 * w1 * Fe, &d_p2));
@@ -1721,6 +1858,7 @@ struct Run {
             EDV_TRY(bilinear_bwd(d_up, d_o1, F, h, w, Fh, 2 * h, 2 * w, false, st));
             EDV_TRY(conv_param_grads(hp + "0", pk, d_o1, h, w, Fe, Fh));
             EDV_TRY(dconv3(d_o1, h, w, Fh, hp + "0", Fe, dst, add ? dst : nullptr));
+            EDV_TRY(bias_flush());  // the next head reuses g.o2 / g.o1 / g.gz
             c->launches += 2;
             return 0;
         };
@@ -1759,10 +1897,10 @@ struct Run {
             EDV_TRY(wsbuf("g.o2", (size_t)F * ih * iw * 32, &d_o2));
             EDV_TRY(wsbuf("g.up", (size_t)F * ih * iw * Fh, &d_up));
             EDV_TRY(wsbuf("g.o1", (size_t)F * h0 * w0 * Fh, &d_o1));
-            if (c->grad_head) EDV_TRY(wsbuf("g.gz", (size_t)F * ih * iw, &gz));  // --train_output_conv (endodav/layers.py:5-34)
+            if (head_params()) EDV_TRY(wsbuf("g.gz", (size_t)F * ih * iw, &gz));  // --train_output_conv (endodav/layers.py:5-34), bias="all"
             EDV_TRY(param("head.scratch.output_conv2.2.weight", &w));
             EDV_TRY(dot_channels_bwd(gd[0], mask0, w, o2, d_o2, gz, (long long)F * ih * iw, 32, 0, st));
-            if (c->grad_head) {
+            if (head_params()) {
                 EDV_TRY(saved("hd.up", &up));
                 EDV_TRY(saved("p1", &p1));
                 EDV_TRY(dot_param_grads("head.scratch.output_conv2.2", o2, gz, (long long)F * ih * iw, 32));
@@ -1770,7 +1908,7 @@ struct Run {
             }
             EDV_TRY(dconv3(d_o2, ih, iw, 32, "head.scratch.output_conv2.0", Fh, d_up));
             EDV_TRY(bilinear_bwd(d_up, d_o1, F, h0, w0, Fh, ih, iw, false, st));
-            if (c->grad_head) EDV_TRY(conv_param_grads("head.scratch.output_conv1", p1, d_o1, h0, w0, Fe, Fh));
+            if (head_params()) EDV_TRY(conv_param_grads("head.scratch.output_conv1", p1, d_o1, h0, w0, Fe, Fh));
             EDV_TRY(dconv3(d_o1, h0, w0, Fh, "head.scratch.output_conv1", Fe, d_p1));
         }
 
@@ -1801,7 +1939,9 @@ struct Run {
         EDV_TRY(motion_module_bwd(0, d_l[3], h3 * w3, oc[2]));
         EDV_TRY(motion_module_bwd(1, d_l[4], h4 * w4, oc[3]));
         const bool res_grads = c->grad_res && cfg.residual_mask != 0;
-        if ((!c->grad_encoder || cfg.lora_type == EDV_LORA_NONE) && !res_grads) {  // temporal-only phase: nothing trainable below the head
+        const bool eb = c->grad_enc_bias, hb = c->grad_head_bias;
+        const bool enc = (c->grad_encoder && cfg.lora_type != EDV_LORA_NONE) || res_grads || eb;  // anything trainable below the head
+        if (!enc && !hb) {  // temporal-only phase: nothing trainable below the head
             c->have_saved = false;
             return 0;
         }
@@ -1812,6 +1952,7 @@ struct Run {
         }
         for (int j = 0; j < 4; ++j) {
             EDV_TRY(wsbuf("g.tap" + std::to_string(j), (size_t)MP * D, &d_tap[j]));
+            if (hb && j != 2) EDV_TRY(wsbuf("g.pj" + std::to_string(j), (size_t)MP * oc[j], &d_pj));  // projects[j]'s dY stays live for its bias
             const float *src = d_pj;
             if (j < 2) {
                 const int s = j == 0 ? 4 : 2;
@@ -1829,7 +1970,11 @@ struct Run {
                 EDV_TRY(dilate2(d_l[4], z, F, ph, pw, oc[3], st));
                 EDV_TRY(dconv3(z, ph, pw, oc[3], "head.resize_layers.3", oc[3], d_pj));
             }
-            EDV_TRY(dgemm(src, MP, oc[j], "head.projects." + std::to_string(j), D, d_tap[j]));
+            if (hb) {  // resize_layers.{0,1,3}: dY of the transposed / stride-2 convolution = d_l; projects[j]: dY = src
+                if (j != 2) EDV_TRY(bias_grad("head.resize_layers." + std::to_string(j) + ".bias", d_l[j + 1], (long long)F * hs_[j + 1] * ws_[j + 1], oc[j]));
+                EDV_TRY(bias_grad("head.projects." + std::to_string(j) + ".bias", src, MP, oc[j]));
+            }
+            if (enc || (hb && cfg.use_clstoken)) EDV_TRY(dgemm(src, MP, oc[j], "head.projects." + std::to_string(j), D, d_tap[j]));
             if (cfg.use_clstoken) {
                 // projects[j] read GELU(W1 tap + (W2 cls + b)) (dpt_pyramid.py:54-57): through the GELU, W1 back to the patch rows,
                 // the per-frame sums of the pre-activation gradient through W2 back to the frame's cls row of the tap
@@ -1837,20 +1982,37 @@ struct Run {
                 const float *pre;
                 float *dpre, *dfb, *part;
                 EDV_TRY(saved("ro" + std::to_string(j) + ".pre", &pre));
-                EDV_TRY(wsbuf("g.ro.dpre", (size_t)MP * D, &dpre));
-                EDV_TRY(wsbuf("g.ro.dfb", (size_t)F * D, &dfb));
-                EDV_TRY(wsbuf("g.ro.part", (size_t)TALL_SPLITS * D, &part));
-                EDV_TRY(wsbuf("g.tapcls" + std::to_string(j), (size_t)F * D, &d_tapcls[j]));
+                EDV_TRY(wsbuf(hb ? "g.ro.dpre" + std::to_string(j) : std::string("g.ro.dpre"), (size_t)MP * D, &dpre));
                 EDV_TRY(ew_bwd(d_tap[j], pre, nullptr, dpre, MP * D, 1, st));
-                for (int f = 0; f < F; ++f) EDV_TRY(col_dot(dpre + (size_t)f * P0 * D, nullptr, P0, D, nullptr, part, dfb + (size_t)f * D, st));
-                EDV_TRY(dgemm(dpre, MP, D, rp + ".w1", D, d_tap[j]));
-                EDV_TRY(dgemm(dfb, F, D, rp + ".w2", D, d_tapcls[j]));
-                c->launches += 3 + 2 * F;
+                if (hb) EDV_TRY(bias_grad(rp + ".bias", dpre, MP, D));  // the pre-GELU gradient over the patch rows
+                c->launches += 1;
+                if (enc) {
+                    EDV_TRY(wsbuf("g.ro.dfb", (size_t)F * D, &dfb));
+                    EDV_TRY(wsbuf("g.ro.part", (size_t)TALL_SPLITS * D, &part));
+                    EDV_TRY(wsbuf("g.tapcls" + std::to_string(j), (size_t)F * D, &d_tapcls[j]));
+                    for (int f = 0; f < F; ++f) EDV_TRY(col_dot(dpre + (size_t)f * P0 * D, nullptr, P0, D, nullptr, part, dfb + (size_t)f * D, st));
+                    EDV_TRY(dgemm(dpre, MP, D, rp + ".w1", D, d_tap[j]));
+                    EDV_TRY(dgemm(dfb, F, D, rp + ".w2", D, d_tapcls[j]));
+                    c->launches += 2 + 2 * F;
+                }
             }
         }
         c->launches += 12;
+        if (!enc) {  // head biases only: the backward stops at the head
+            EDV_TRY(bias_finish());
+            c->have_saved = false;
+            return 0;
+        }
+        if (eb) {  // pretrained.norm.bias: the final norm's dy at all four taps and, with use_clstoken, at every frame's token 0
+            std::vector<BiasSrc> srcs;
+            for (int j = 0; j < 4; ++j) srcs.push_back(BiasSrc{d_tap[j], MP, D, identity_map()});
+            if (cfg.use_clstoken)
+                for (int j = 0; j < 4; ++j) srcs.push_back(BiasSrc{d_tapcls[j], (long long)F, D, identity_map()});
+            EDV_TRY(bias_grad("pretrained.norm.bias", srcs, D));
+        }
 
         // ---------------- encoder ----------------
+        if (!eb) EDV_TRY(bias_flush());  // the head's bias jobs (only encoder jobs share the encoder's flushes)
         float *dxt, *t1, *t3, *t4, *delta, *lws;
         EDV_TRY(wsbuf("g.xt", (size_t)MT * D, &dxt));
         EDV_TRY(wsbuf("g.e1", (size_t)MT * D, &t1));
@@ -1896,9 +2058,17 @@ struct Run {
             EDV_TRY(ew_bwd(t4, pre, nullptr, t4, MT * 4 * D, 1, st));
             if (lora) EDV_TRY(lora_step(bp + ".mlp.fc1", xn2, D, t4, 4 * D, MT, rank, lscale, "", lws, lws_n));
             EDV_TRY(dgemm(t4, MT, 4 * D, bp + ".mlp.fc1", D, t1));
+            if (eb) {  // dxt is about to gain norm2's input gradient, t1 / t4 are reused: the MLP's biases now
+                const float *g2;
+                EDV_TRY(param(bp + ".ls2.gamma", &g2));
+                EDV_TRY(bias_grad(bp + ".mlp.fc2.bias", dxt, MT, D, g2));  // LayerScale multiplies the bias (folded into W and the epilogue)
+                EDV_TRY(bias_grad(bp + ".mlp.fc1.bias", t4, MT, 4 * D));    // the pre-activation gradient
+                EDV_TRY(bias_grad(bp + ".norm2.bias", t1, MT, D));
+                EDV_TRY(bias_flush());
+            }
             EDV_TRY(param(bp + ".norm2.weight", &w2));
             EDV_TRY(layernorm_bwd(x_mid, identity_map(), w2, t1, identity_map(), dxt, identity_map(), MT, D, 1e-6f, true, st));
-            if (i == 0) break;  // nothing trainable below block 0's MLP
+            if (i == 0 && !eb) break;  // nothing trainable below block 0's MLP
             // x_mid = x_in + ls1 * proj(attn(qkv(norm1(x_in))))
             EDV_TRY(dgemm(dxt, MT, D, bp + ".attn.proj", D, t1));
             {
@@ -1906,10 +2076,21 @@ struct Run {
                 EDV_TRY(attn_spatial_bwd(qkv, att, t1, lse, delta, t3, F, ntok, heads, abws, abws_n, st));
             }
             EDV_TRY(dgemm(t3, MT, 3 * D, bp + ".attn.qkv", D, t1));
+            if (eb) {
+                const float *g1;
+                EDV_TRY(param(bp + ".ls1.gamma", &g1));
+                EDV_TRY(bias_grad(bp + ".attn.proj.bias", dxt, MT, D, g1));
+                EDV_TRY(bias_grad(bp + ".attn.qkv.bias", t3, MT, 3 * D));
+                EDV_TRY(bias_grad(bp + ".norm1.bias", t1, MT, D));
+                EDV_TRY(bias_flush());
+            }
             EDV_TRY(param(bp + ".norm1.weight", &w2));
             EDV_TRY(layernorm_bwd(x_in, identity_map(), w2, t1, identity_map(), dxt, identity_map(), MT, D, 1e-6f, true, st));
             c->launches += 6;
+            if (i == 0)  // bias="all" went on through block 0: x_0 = patch_embed(x) + pos on the patch rows, the cls row does not see the bias
+                EDV_TRY(bias_grad("pretrained.patch_embed.proj.bias", {BiasSrc{dxt, MP, D, RowMap{P0, ntok, c0}}}, D));
         }
+        EDV_TRY(bias_finish());
         c->have_saved = false;
         return 0;
     }
@@ -2159,6 +2340,13 @@ int edv_set_grad_scope(edv_ctx *ctx, int32_t encoder_factors, int32_t temporal_f
     ctx->grad_encoder = encoder_factors != 0;
     ctx->grad_temporal = temporal_factors != 0;
     ctx->grad_head = head_convs != 0;
+    return 0;
+}
+
+int edv_set_bias_grads(edv_ctx *ctx, int32_t encoder_biases, int32_t head_biases) {
+    EDV_CHECK(ctx, "null context");
+    ctx->grad_enc_bias = encoder_biases != 0;
+    ctx->grad_head_bias = head_biases != 0;
     return 0;
 }
 

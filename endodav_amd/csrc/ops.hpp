@@ -162,6 +162,29 @@ int conv3_wgrad(const float *x, const float *dy, float *dw, int F, int H, int W,
 // out[n] (+)= sum_m rowscale[m] * P[m, n]  (rowscale may be null; N a power of two in 4..1024, or 1): bias gradients, 1x1-conv weight gradient
 size_t colsum_workspace(int N);  // floats
 int colsum_rows(const float *P, const float *rowscale, long long M, int N, float *ws, size_t ws_floats, float *out, bool accumulate, hipStream_t st);
+// batched column sums of the bias gradients (bias_colsum.hip): stage 1 writes per-chunk partial rows of each job into its slab region,
+// stage 2 adds an output's consecutive partial rows in a fixed order (no atomics), times scale[n], into dst (or onto it)
+constexpr int CS_MAX_JOBS = 16, CS_MAX_OUTS = 48, CS_MAX_PARTS = 64;
+struct ColsumJob {
+    const float *src = nullptr;
+    long long ld = 0, rows = 0, chunk = 0;
+    RowMap map{0, 0, 0};
+    int N = 0, parts = 0, cw_log = 0;
+    float *slab = nullptr;  // [parts, N]
+};
+struct ColsumOut {
+    const float *slab;  // [rows, N] partial rows
+    int rows, N;
+    const float *scale;  // per-column factor, or null
+    float *dst;
+    int accumulate;
+};
+ColsumJob colsum_job(const float *src, long long ld, long long rows, RowMap map, int N);  // sets parts / chunk; the caller sets slab
+int colsum_stage1_launch(const ColsumJob *jobs, int n, hipStream_t st);
+int colsum_stage2_launch(const ColsumOut *outs, int n, hipStream_t st);
+size_t colsum_batch_workspace(int n, const long long *rows, const int *cols);  // floats
+int colsum_batch(int n, const float *const *src, const long long *ld, const long long *rows, const RowMap *maps, const int *cols, const float *const *scale,
+                 float *const *dst, const int *accumulate, float *ws, size_t ws_floats, hipStream_t st);
 int groupnorm_bwd(const float *x, const float *stats, const float *w, const float *dy, float *sums, float *dx, int F, int P, int C, int groups, bool accumulate,
                   hipStream_t st);
 int attn_temporal_bwd(const float *qkv, const float *dout, float *dqkv, int B, int T, int P, int C, int heads, hipStream_t st);

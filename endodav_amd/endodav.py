@@ -355,6 +355,31 @@ def _is_head_conv(name: str) -> bool:
     return (name.startswith("head.conv_depth_") or name.startswith("head.scratch.output_conv")) and name.rsplit(".", 1)[-1] in ("weight", "bias")
 
 
+def _is_bias(name: str) -> bool:
+    """A parameter that mark_only_part_as_trainable(bias="all") unfreezes (endodav/layers.py:5-34: every name containing "bias")."""
+    return name.endswith(".bias")
+
+
+def _is_unreached(name: str) -> bool:
+    """refinenet4.resConfUnit1 exists but the forward never calls it (dpt_pyramid.py:81): its gradient stays None, as in the reference."""
+    return name.startswith("head.scratch.refinenet4.resConfUnit1.")
+
+
+def grad_scope(names: Sequence[str]) -> Tuple[int, int, int, int, int, int]:
+    """The engine's gradient scope for a set of trainable state_dict names: (encoder_factors, temporal_factors, head_convs, residual_blocks)
+    for edv_set_grad_scope and (encoder_biases, head_biases) for edv_set_bias_grads.  A bias that an existing scope already produces (the
+    output-head convolutions, the residual blocks) does not turn the bias scopes on."""
+    enc = any(_is_lora_factor(n) and ".mlp.fc" in n for n in names)
+    tmp = any(_is_lora_factor(n) and ".ff.net.2." in n for n in names)
+    hd = any(_is_head_conv(n) and not _is_bias(n) for n in names)
+    rb = any(n.startswith("pretrained.blocks.") and ".residual_." in n for n in names)
+    eb = any(_is_bias(n) and n.startswith("pretrained.") and ".residual_." not in n for n in names)
+    hb = any(_is_bias(n) and n.startswith("head.") and not _is_head_conv(n) for n in names)
+    if any(_is_head_conv(n) and _is_bias(n) for n in names) and not hd:
+        hb = True  # a head convolution's bias without its weight: produced by the bias scope
+    return int(enc), int(tmp), int(hd), int(rb), int(eb), int(hb)
+
+
 class _NativeCtx:
     """Owns one ``edv_ctx`` (one device).  Destroyed with the last module/replica that references it."""
 
@@ -436,10 +461,7 @@ class _EdvFunction(torch.autograd.Function):
             gs = [(g.detach().contiguous().float() if g is not None else torch.zeros(shp, device=ctx.device)) for g, shp in zip(gouts, ctx.shapes)]
             ptrs = (C.c_void_p * 4)(*[g.data_ptr() for g in gs])
             stream = C.c_void_p(_lib.stream_ptr(ctx.device))
-            enc = any(".mlp.fc" in n for n in ctx.names)
-            tmp = any(".ff.net.2." in n for n in ctx.names)
-            hd = any(_is_head_conv(n) for n in ctx.names)
-            rb = any(".residual_." in n for n in ctx.names)
+            enc, tmp, hd, rb, eb, hb = grad_scope(ctx.names)
             shapes = [tuple(p.shape) for p in ctx.params]
             fg = nat.flat
             if fg is None or fg.names != ctx.names or fg.shapes != shapes:
@@ -448,7 +470,8 @@ class _EdvFunction(torch.autograd.Function):
             # overwritten by the engine before autograd could add to it.  Keep the old sums and add them back in place.
             held = [i for i, p in enumerate(ctx.params) if p.is_leaf and fg.aliases(i, p.grad)]
             prev = fg.flat.clone() if held else None
-            _lib.check(lib.edv_set_grad_scope(C.c_void_p(nat.handle), int(enc), int(tmp), int(hd), int(rb)), "edv_set_grad_scope")
+            _lib.check(lib.edv_set_grad_scope(C.c_void_p(nat.handle), enc, tmp, hd, rb), "edv_set_grad_scope")
+            _lib.check(lib.edv_set_bias_grads(C.c_void_p(nat.handle), eb, hb), "edv_set_bias_grads")
             _lib.check(lib.edv_backward(C.c_void_p(nat.handle), C.c_uint64(ctx.generation), disp0.data_ptr(), ptrs, stream), "edv_backward")
             grads: List[Optional[torch.Tensor]] = fg.views()
             if held:
@@ -583,8 +606,9 @@ class endodav(nn.Module):
             sd.update({k: v for k, v in self.named_buffers() if k.endswith(".freqs_cis")})
         sig = tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
         if sig != nat.sig and nat.sig is not None and len(sig) == len(nat.sig) and all(
-                a[:2] == b[:2] and (a[2] == b[2] or _is_lora_factor(a[0]) or _is_head_conv(a[0]) or ".residual_." in a[0]) for a, b in zip(sig, nat.sig)):
-            # the fine-tune loop: same tensors, only trainable ones written (optimizer.step) -> re-fold / re-pack those only
+                a[:2] == b[:2] and (a[2] == b[2] or _is_lora_factor(a[0]) or _is_head_conv(a[0]) or ".residual_." in a[0] or _is_bias(a[0]))
+                for a, b in zip(sig, nat.sig)):
+            # the fine-tune loop: same tensors, only trainable ones written (optimizer.step) -> re-fold / re-pack those only (biases: bias="all")
             _lib.check(lib.edv_refresh_lora(C.c_void_p(nat.handle), C.c_void_p(_lib.stream_ptr(device))), "edv_refresh_lora")
             nat.sig = sig
         if sig != nat.sig:
@@ -700,13 +724,16 @@ class endodav(nn.Module):
     def _trainable_names(self) -> List[str]:
         """state_dict names of the parameters that require grad, in state_dict order.  The HIP backward produces the
         gradients of the LoRA factors of mlp.fc1 / mlp.fc2 (what ``mark_only_part_as_trainable`` leaves trainable for
-        lora / dvlora, endodav/layers.py:5-34); a trainable parameter outside that set is refused, not silently frozen."""
-        names = [n for n, p in self.state_dict(keep_vars=True).items() if p.requires_grad]
-        bad = [n for n in names if not (_is_lora_factor(n) or _is_head_conv(n) or (n.startswith("pretrained.blocks.") and ".residual_." in n))]
+        lora / dvlora, endodav/layers.py:5-34), residual_*, the output-head convolutions and, for bias="all", every bias; a trainable
+        parameter outside that set is refused, not silently frozen.  The biases of refinenet4.resConfUnit1, which the forward never
+        reaches, are left out: their .grad stays None, as in the reference."""
+        names = [n for n, p in self.state_dict(keep_vars=True).items() if p.requires_grad and not (_is_bias(n) and _is_unreached(n))]
+        bad = [n for n in names if not (_is_lora_factor(n) or _is_head_conv(n) or (n.startswith("pretrained.blocks.") and ".residual_." in n) or _is_bias(n))]
         if bad:
             raise NotImplementedError(f"libendodav_hip has no gradient for {bad[:4]}{' ...' if len(bad) > 4 else ''}: the HIP backward covers the LoRA "
                                       "factors of the encoder MLPs (and, with temporal_lora, of ff.net.2 in the motion modules), the residual bottleneck "
-                                      "blocks residual_* and the output-head convolutions conv_depth_* / scratch.output_conv* (SURVEY.md §8f rank 3)")
+                                      "blocks residual_*, the output-head convolutions conv_depth_* / scratch.output_conv* and every bias (bias=\"all\") "
+                                      "(SURVEY.md §8f rank 3)")
         if any(_is_lora_factor(n) for n in names) and self.lora_type not in ("lora", "dvlora", "ssb", "dash"):
             raise NotImplementedError(f"the HIP backward supports lora_type 'lora', 'dvlora', 'ssb' and 'dash', not {self.lora_type!r}")
         return names
@@ -771,7 +798,8 @@ class endodav(nn.Module):
             return None
         sd = self.state_dict(keep_vars=True)
         mine = [sd.get(n) for n in fg.names]
-        wanted = {id(p) for p in params if p.requires_grad}
+        unreached = {id(v) for k, v in sd.items() if _is_bias(k) and _is_unreached(k)}  # trainable under bias="all", never reached: .grad None
+        wanted = {id(p) for p in params if p.requires_grad and id(p) not in unreached}
         if {id(p) for p in mine} != wanted or any(p is None for p in mine):
             return None
         if not all(fg.aliases(i, p.grad) for i, p in enumerate(mine)):

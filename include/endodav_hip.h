@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define EDV_ABI_VERSION 10 /* 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
+#define EDV_ABI_VERSION 11 /* 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
 
 enum edv_lora_type { EDV_LORA_NONE = 0, EDV_LORA_LORA = 1, EDV_LORA_DVLORA = 2, EDV_LORA_SSB = 3, EDV_LORA_DASH = 4 };
 
@@ -86,7 +86,8 @@ int edv_prepare(edv_ctx *ctx, void *stream);
 /* The cheap form of edv_prepare for the fine-tune loop (trainer_end_to_end_video.py:427-431: only the optimizer writes, and only
  * into trainable tensors): re-folds the linears that carry LoRA factors (mlp.fc1/fc2 of every block and, with temporal_lora, ff.net.2
  * of the motion modules), re-packs the trainable convolutions (conv_depth_* or scratch.output_conv*, residual_*) and, once a backward
- * has run, their transposed / flipped copies.  Everything frozen keeps its packing.  Valid only when no bound pointer changed and
+ * has run, their transposed / flipped copies, and rebuilds the packings that embed a copy of a bias (resize_layers.0/1, the fused
+ * GEGLU weights of the motion modules, with use_bn the BatchNorm-folded ResidualConvUnit convolutions).  Everything else keeps its packing.  Valid only when no bound pointer changed and
  * only those tensors' contents did; otherwise call edv_prepare. */
 int edv_refresh_lora(edv_ctx *ctx, void *stream);
 
@@ -269,10 +270,11 @@ int edv_fold_lora(const float *W_dev, const float *A_dev, const float *B_dev, co
  * the kept activations is an error, never a silently wrong gradient.  disp0 = the ("disp", 0) map that forward wrote,
  * grads[k] = dL/d("disp", k), k = 0..3 (all four required, contiguous fp32).  Produces the gradients edv_set_grad_scope selects,
  * named like the state_dict: the LoRA factors of mlp.fc1 / mlp.fc2 ("pretrained.blocks.<i>.mlp.fc<j>.lora_{A,B,U,V,index}"), with
- * temporal_lora those of ff.net.2 in the motion modules, the output-head convolutions, the residual blocks -- the trainable sets
- * of endodav/layers.py:5-34.  Where they land: a name listed in the caller's flat buffer (edv_grad_bind_flat) is written into its
+ * temporal_lora those of ff.net.2 in the motion modules, the output-head convolutions, the residual blocks, the biases -- the trainable sets
+ * of endodav/layers.py:5-34 -- and, under edv_set_bias_grads, the biases (bias="all").  Where they land: a name listed in the caller's flat buffer (edv_grad_bind_flat) is written into its
  * slice there; any other into context-owned memory, read with edv_grad / edv_grad_copy.
- * After the optimizer step call edv_refresh_lora (or edv_prepare) before the next forward. */
+ * After the optimizer step call edv_refresh_lora (or edv_prepare) before the next forward; edv_refresh_lora also covers any change of a
+ * bias. */
 int edv_set_train(edv_ctx *ctx, int32_t on);
 /* Which gradients the next edv_backward has to produce.  The trainer alternates spatial and temporal tuning phases
  * (trainer_end_to_end_video.py:327-339); with encoder_factors = 0 the backward stops at the head (nothing below it is
@@ -283,6 +285,14 @@ int edv_set_train(edv_ctx *ctx, int32_t on);
  * ("pretrained.blocks.<i>.residual_.{conv1,conv2,conv3}.weight", ".norm{1,2,3}.{weight,bias}"; trainable by default in the reference,
  * block.py:146-150).  Default: both factor sets, nothing else. */
 int edv_set_grad_scope(edv_ctx *ctx, int32_t encoder_factors, int32_t temporal_factors, int32_t head_convs, int32_t residual_blocks);
+/* The bias gradients of mark_only_part_as_trainable(bias="all") (endodav/layers.py:5-34), on top of edv_set_grad_scope's sets.
+ * encoder_biases != 0: every "pretrained.*bias" (patch_embed.proj, each block's norm1/2, attn.qkv/proj, mlp.fc1/fc2, residual_.norm1..3 if
+ * present, the final norm); the backward then also runs block 0's attention and patch-embedding backward.  head_biases != 0: every
+ * "head.*bias" the forward reaches (projects, resize_layers, readout_projects, the motion modules, refinenet* out_conv / resConfUnit
+ * convolutions, conv_depth_* or output_conv*); refinenet4.resConfUnit1 is never reached and gets none.  With head_biases alone the
+ * backward stops at the head.  Default 0 / 0.  Each bias gradient is one column sum of the dY of its operator (times the LayerScale
+ * gamma for attn.proj / mlp.fc2), reduced in a fixed order: bit-reproducible. */
+int edv_set_bias_grads(edv_ctx *ctx, int32_t encoder_biases, int32_t head_biases);
 int edv_generation(const edv_ctx *ctx, uint64_t *generation);
 int edv_backward(edv_ctx *ctx, uint64_t generation, const float *disp0_dev, const float *const grad_disp_dev[4], void *stream);
 /* One contiguous gradient buffer owned by the caller, for the data-parallel step (the reference's nn.DataParallel reduce,
@@ -387,6 +397,13 @@ int edv_conv3x3_wgrad(const float *x_dev, const float *dy_dev, float *dw_dev, in
 size_t edv_colsum_workspace(int32_t N); /* bytes */
 int edv_colsum_rows(const float *P_dev, const float *rowscale_dev, int64_t M, int32_t N, float *workspace_dev, size_t workspace_bytes, float *out_dev,
                     int32_t accumulate, void *stream);
+/* Batched column sums (the bias gradients of bias="all"): for job k, dst[k][n] (+)= scale[k][n] * sum_m P_k[map_k(m), n] over rows[k] rows,
+ * P_k = src[k] with leading dimension ld[k], n < cols[k] (any cols >= 1).  row_map (optional) = n triples (period, stride, offset): row m
+ * reads physical row (m / period) * stride + offset + m % period (period 0 = identity).  scale (optional, entries may be NULL) and
+ * accumulate (optional) per job.  Two launches for all jobs, fixed summation order (bit-reproducible), no atomics. */
+size_t edv_colsum_batch_workspace(int32_t n, const int64_t *rows, const int32_t *cols); /* bytes */
+int edv_colsum_batch(int32_t n, const float *const *src_dev, const int64_t *ld, const int64_t *rows, const int32_t *row_map, const int32_t *cols,
+                     const float *const *scale_dev, float *const *dst_dev, const int32_t *accumulate, float *workspace_dev, size_t workspace_bytes, void *stream);
 /* GroupNorm input gradient; stats = the forward's [F, groups, 2] (mean, rstd); sums = [F, groups, 2] scratch. */
 int edv_groupnorm_bwd(const float *x_dev, const float *stats_dev, const float *w_dev, const float *dy_dev, float *sums_dev, float *dx_dev, int32_t F,
                       int32_t P, int32_t C, int32_t groups, int32_t accumulate, void *stream);
