@@ -17,6 +17,7 @@ const char *edv_last_error(void) { return edv::get_error(); }
 
 int edv_create(const edv_config *cfg, edv_ctx **out) {
     EDV_CHECK(cfg && out, "null argument");
+    *out = nullptr;  // every check comes before the allocation: an error leaves the handle null and nothing to free
     EDV_CHECK(cfg->abi_version == EDV_ABI_VERSION, "ABI version mismatch");
     EDV_CHECK(cfg->embed_dim > 0 && cfg->num_heads > 0 && cfg->embed_dim == cfg->num_heads * 64, "head dim must be 64");
     EDV_CHECK(cfg->embed_dim <= 1024, "embed_dim > 1024 unsupported");
@@ -32,15 +33,13 @@ int edv_create(const edv_config *cfg, edv_ctx **out) {
     EDV_CHECK(cfg->depth <= 32 && (cfg->depth == 32 || (cfg->residual_mask >> cfg->depth) == 0), "residual_mask names a block >= depth");
     EDV_CHECK(cfg->residual_mask == 0 || (cfg->embed_dim / 8) % 4 == 0, "residual blocks need embed_dim / 8 to be a multiple of 4");
     for (int j = 0; j < 4; ++j) EDV_CHECK(cfg->taps[j] >= 0 && cfg->taps[j] < cfg->depth && (j == 0 || cfg->taps[j] > cfg->taps[j - 1]), "taps");
+    const char *products = getenv("EDV_PRODUCTS");  // "f32" | "bf16x6": initial arithmetic of the encoder's linears (edv_set_products changes it)
+    EDV_CHECK(!products || !strcmp(products, "f32") || !strcmp(products, "bf16x6"), "EDV_PRODUCTS must be f32 or bf16x6");
     *out = new edv_ctx();
     (*out)->cfg = *cfg;
     if (hipGetDevice(&(*out)->device) != hipSuccess) (*out)->device = -1;  // no device visible (host-only checks of the configuration)
     if (const char *e = getenv("EDV_ENC_STREAMS")) (*out)->enc_streams = (*out)->enc_streams_initial = atoi(e);
-    if (const char *e = getenv("EDV_PRODUCTS")) {  // "f32" | "bf16x6": initial arithmetic of the encoder's linears (edv_set_products changes it)
-        const std::string v(e);
-        EDV_CHECK(v == "f32" || v == "bf16x6", "EDV_PRODUCTS must be f32 or bf16x6");
-        (*out)->products = v == "bf16x6" ? EDV_PRODUCTS_BF16X6 : EDV_PRODUCTS_F32;
-    }
+    if (products) (*out)->products = !strcmp(products, "bf16x6") ? EDV_PRODUCTS_BF16X6 : EDV_PRODUCTS_F32;
     return 0;
 }
 

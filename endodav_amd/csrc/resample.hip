@@ -170,16 +170,31 @@ __global__ void bicubic_pos_kernel(const float *__restrict__ grid, float *__rest
     out[i] = acc;
 }
 
+// Half-pixel source coordinate of output index o, (o + 0.5) * n / on - 0.5 = ((2 o + 1) n - on) / (2 on), split into floor and fraction in
+// integers.  In fp32 the coordinate of a full-HD frame carries an absolute error of 6e-5 (one ulp at 1024), which the cubic turns into 1e-4 of
+// the image's range -- ATen's own fp32 bicubic is that far from the fp64 result; the fraction below is exact to fp32 rounding at any size.
+__device__ __forceinline__ void cubic_source(int o, int n, int on, int &i0, float &t) {
+    const int num = (2 * o + 1) * n - on, den = 2 * on;  // |num| < 2^31: checked by the launcher
+    int q = num / den, r = num - q * den;
+    if (r < 0) {
+        r += den;
+        --q;
+    }
+    i0 = q;
+    t = (float)r / (float)den;
+}
+
 // planar image resize with the same cubic (cv2.INTER_CUBIC / ATen bicubic, align_corners=False)
-__global__ void resize_bicubic_kernel(const float *__restrict__ x, float *__restrict__ y, int NP, int H, int W, int OH, int OW, float rh, float rw) {
+__global__ void resize_bicubic_kernel(const float *__restrict__ x, float *__restrict__ y, int NP, int H, int W, int OH, int OW) {
     const long long total = (long long)NP * OH * OW;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int ox = (int)(i % OW);
         const int oy = (int)((i / OW) % OH);
         const long long pl = i / ((long long)OW * OH);
-        const float sy = __fsub_rn(__fmul_rn(rh, (float)oy + 0.5f), 0.5f), sx = __fsub_rn(__fmul_rn(rw, (float)ox + 0.5f), 0.5f);
-        const int iy = (int)floorf(sy), ix = (int)floorf(sx);
-        const float ty = sy - (float)iy, tx = sx - (float)ix;
+        int iy, ix;
+        float ty, tx;
+        cubic_source(oy, H, OH, iy, ty);
+        cubic_source(ox, W, OW, ix, tx);
         const float wy[4] = {cc2(ty + 1.f), cc1(ty), cc1(1.f - ty), cc2(2.f - ty)};
         const float wx[4] = {cc2(tx + 1.f), cc1(tx), cc1(1.f - tx), cc2(2.f - tx)};
         const float *src = x + pl * H * W;
@@ -267,8 +282,8 @@ int sigmoid_inplace(float *x, long long n, hipStream_t st) {
 
 int resize_bicubic(const float *x, float *y, int NP, int H, int W, int OH, int OW, hipStream_t st) {
     EDV_CHECK(x && y && NP > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "bad operand");
-    EDV_LAUNCH(resize_bicubic_kernel, dim3(grid_for((long long)NP * OH * OW, 16384)), dim3(256), 0, st, x, y, NP, H, W, OH, OW,
-                       (float)H / (float)OH, (float)W / (float)OW);
+    EDV_CHECK(2ll * OH * H + OH < (1ll << 31) && 2ll * OW * W + OW < (1ll << 31), "resize_bicubic: input size x output size beyond 2^30 per axis");
+    EDV_LAUNCH(resize_bicubic_kernel, dim3(grid_for((long long)NP * OH * OW, 16384)), dim3(256), 0, st, x, y, NP, H, W, OH, OW);
     EDV_LAUNCH_OK();
     return 0;
 }

@@ -91,7 +91,9 @@ class ClipsInFlight:
     def next_lane(self, frames: int):
         """(stream, lane id) for the next clip of ``frames`` frames, round-robin: for pipelines that put more than the forward on the lane's stream
         (``video.HipWindowRunner``: uint8 -> float, pre-resize, forward, resize back).  The caller runs ``model(x, lane=lane)`` under
-        ``torch.cuda.stream(stream)`` and orders its own inputs / outputs with events."""
+        ``torch.cuda.stream(stream)`` and orders its own inputs / outputs with events.  Unlike ``submit``, this does NOT make the lane wait for the
+        caller's stream: the first forward on a lane folds and packs the weights on the lane's stream, so the caller orders that stream after
+        whatever last wrote them (``HipWindowRunner.run`` records one event on its caller's stream and has every lane wait for it)."""
         if self.depth is None:
             self.depth = self.auto_depth(self.model, frames)
         while len(self.streams) < self.depth:

@@ -13,9 +13,11 @@ Differences in *where* work happens, not in what is computed:
 
 The cv2.INTER_CUBIC pre-resize is "parity unpinned" (cv2 is absent from the build
 container and the reference has no fixture for it); the kernel implements the published algorithm
-(Keys cubic, a = -0.75, half-pixel centres, clamped borders).  When the frames already have the
-network's size the resize is the identity and the whole path is pinned by ``tests/test_video_gpu.py``
-(windowing, key frames, stitching: reference golden) and ``tests/test_host_cpu.py`` (the host logic alone).
+(Keys cubic, a = -0.75, half-pixel centres, clamped borders) and is held to it in fp64 at the sizes a
+video feeds it (``tests/test_kernels_gpu.py``).  When the frames already have the network's size the
+resize is the identity (bit for bit) and the whole path is pinned by ``tests/test_video_gpu.py``
+(windowing, key frames, stitching: reference goldens of 2 and 6 windows; the pipelined runner against
+the window-by-window forward) and ``tests/test_host_cpu.py`` (the host logic alone).
 """
 from __future__ import annotations
 
@@ -145,9 +147,13 @@ class HipWindowRunner:
             # engine context and stream (pipeline.ClipsInFlight; depth by auto_depth: 3 lanes at the reference's 224 x 280, one at 518 x 518 where a
             # 32-frame window fills the part alone -- ViT-S 224 x 280 T=32: 4140 -> 4380..4760 frames/s, profiles/r03_notes.txt).  A lane's stream
             # carries the whole per-window chain: uint8 -> float, pre-resize, forward, resize back.
-            depth = ClipsInFlight.auto_depth(self.model, INFER_LEN)
-            flight = getattr(self.model, "_video_flight", None)  # kept with the model: a lane's engine context (packed weights, workspace) is built once
-            if flight is None or flight.dev != dev or flight.depth != depth:
+            # A lora_type="dash" model counts its forwards (one DashLinear call counter per model, switched on after 100 calls) and so has one
+            # engine context only: its windows run one at a time on lane 0, on one stream of this runner, one _dash_step per window in window
+            # order -- the reference's sequence of forward calls.  The copies still overlap the forward.
+            dash = getattr(self.model, "lora_type", None) == "dash"
+            depth = 1 if dash else ClipsInFlight.auto_depth(self.model, INFER_LEN)
+            flight = None if dash else getattr(self.model, "_video_flight", None)  # kept with the model: a lane's engine context (packed weights, workspace) is built once
+            if not dash and (flight is None or flight.dev != dev or flight.depth != depth):
                 flight = ClipsInFlight(self.model, dev, depth=depth)
                 try:
                     self.model._video_flight = flight
@@ -155,6 +161,14 @@ class HipWindowRunner:
                     pass
             nbuf = min(depth + 1, len(sources))
             s_in, s_out = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+            s_dash = torch.cuda.Stream(device=dev) if dash else None
+            # Stream contract: run() orders itself after everything the caller has enqueued on its current stream so far -- an optimizer.step() or
+            # load_state_dict whose weights the first forward on a lane folds and packs, and earlier users of the memory the buffers below get
+            # from that stream's allocator pool, which are first written on the streams of this runner.  The copy-in stream and every lane wait
+            # for this event once; the copy-out stream follows the lanes.  All work is drained before run() returns host arrays.
+            entry = torch.cuda.Event()
+            entry.record(torch.cuda.current_stream(dev))
+            s_in.wait_event(entry)
             h_in = [torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8).pin_memory() for _ in range(nbuf)]
             d_in = [torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
             h_out = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32).pin_memory() for _ in range(nbuf)]
@@ -187,7 +201,9 @@ class HipWindowRunner:
                 if k + 1 < len(sources):
                     upload(k + 1)                     # overlaps the windows in flight
                 drain(slot)                           # frees d_out[slot] / h_out[slot] (window k - nbuf's copy), in window order
-                stream, lane = flight.next_lane(INFER_LEN)
+                stream, lane = (s_dash, 0) if dash else flight.next_lane(INFER_LEN)
+                if k < depth:
+                    stream.wait_event(entry)          # the lanes come round-robin: the first `depth` windows reach each of them once
                 with torch.cuda.stream(stream):
                     st = C.c_void_p(_lib.stream_ptr(dev))
                     stream.wait_event(up_done[slot])

@@ -147,6 +147,55 @@ def make_video_golden(ref):
     print(f"video_stitch: {len(seen)} windows, out mean {out.mean():.4f}; wrote {os.path.getsize(path)} B")
 
 
+VIDEO_LONG_CASE = dict(n_frames=120, h=28, w=42)  # 6 windows; the last one is 22 copies of the final frame behind 10 key frames
+
+
+def long_video_frames(n: int, h: int, w: int) -> np.ndarray:
+    """uint8 frames [n, h, w, 3] whose means identify them: noise in [0, 0.2] on a per-frame offset 0.8 * i / n.  (With plain uniform noise two
+    frames of this size came within 2e-6 of each other's mean, so a wrong key frame could have hidden in ``window_input_means``.)"""
+    from endodav_amd import synth
+
+    ramp = (0.8 * np.arange(n, dtype=np.float32) / n)[:, None, None, None]
+    return ((synth.uniform("video_long:frames", (n, h, w, 3), 0.0, 0.2) + ramp) * 255).astype(np.uint8)
+
+
+def save_npz_stable(path: str, **arrays) -> None:
+    """np.savez_compressed with a fixed member time stamp, so that regenerating a fixture reproduces its bytes."""
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def make_video_long_golden(ref):
+    """A video long enough for what two windows never do (reference endodav.py:185-254, same recipe as make_video_golden): the key-frame chain
+    over three and more windows, alignment to an already re-scaled predecessor, a last window that is mostly padding."""
+    n, h, w = VIDEO_LONG_CASE["n_frames"], VIDEO_LONG_CASE["h"], VIDEO_LONG_CASE["w"]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        model = ref.endodav(encoder="vits", features=32, out_channels=[32, 32, 64, 64], image_shape=(h, w), lora_type="none",
+                            disable_conv_head=True, pretrained_path=None).eval()
+    frames = long_video_frames(n, h, w)
+    means = np.sort((frames.astype(np.float32) / 255.0).mean(axis=(1, 2, 3), dtype=np.float64))
+    assert np.diff(means).min() >= 1e-3, f"two frames' means are {np.diff(means).min():.2e} apart: a wrong key frame could hide"
+    seen = []
+
+    def recorder(x):
+        seen.append(x[0].mean(dim=(1, 2, 3)).numpy().astype(np.float64))  # per-frame mean of the window input
+        return {("disp", 0): torch.from_numpy(fake_window_disp(len(seen) - 1, h, w))}
+
+    model.forward = recorder
+    out = model.infer_video_depth(frames, device="cpu")
+    assert out.shape == (n, h, w) and len(seen) == 6
+    path = os.path.join(HERE, "video_stitch_long.npz")
+    save_npz_stable(path, out=out.astype(np.float32), window_input_means=np.stack(seen))
+    print(f"video_stitch_long: {len(seen)} windows, out mean {out.mean():.4f}; wrote {os.path.getsize(path)} B")
+
+
 def metrics_inputs():
     """Deterministic inputs of the metric known-answer test (regenerated identically by tests/test_evaluate_cpu.py)."""
     from endodav_amd import synth
@@ -414,6 +463,8 @@ def main(argv):
     ref = load_reference()
     if not argv or "video" in argv:
         make_video_golden(ref)
+    if not argv or "video_long" in argv:
+        make_video_long_golden(ref)
     if not argv or "keys" in argv:
         dump_state_keys(ref)
     if not argv or "metrics" in argv:
@@ -422,7 +473,7 @@ def main(argv):
         make_loss_kat()
     if not argv or "trainer_losses" in argv:
         make_trainer_loss_kat()
-    names = [a for a in argv if a not in ("video", "keys", "metrics", "losses", "trainer_losses")] if argv else list(CASES)
+    names = [a for a in argv if a not in ("video", "video_long", "keys", "metrics", "losses", "trainer_losses")] if argv else list(CASES)
     torch.set_num_threads(8)
     for name in names:
         kwargs, (B, T, H, W), kind, store = CASES[name]

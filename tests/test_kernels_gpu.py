@@ -519,12 +519,57 @@ def test_bicubic_pos(lib, cuda, S, oh, ow):
 
 @pytest.mark.parametrize("H,W,OH,OW", [(480, 640, 518, 686), (1024, 1280, 518, 644), (50, 60, 100, 120)])
 def test_resize_bicubic(lib, cuda, H, W, OH, OW):
+    # fp64 reference: ATen's fp32 bicubic evaluates the source coordinate in fp32 and is itself 4e-5 .. 9e-5 of the range away from the fp64
+    # result at these sizes (test_resize_bicubic_against_fp64 prints it); the kernel splits the coordinate in integers
     x = torch.rand(3, 1, H, W, generator=torch.Generator().manual_seed(5))
-    ref = F.interpolate(x, size=(OH, OW), mode="bicubic", align_corners=False)
+    ref = F.interpolate(x.double(), size=(OH, OW), mode="bicubic", align_corners=False)
     xd = x.to(cuda)
     y = torch.empty(3, 1, OH, OW, device=cuda)
     _lib.check(lib.edv_resize_bicubic(xd.data_ptr(), y.data_ptr(), 3, H, W, OH, OW, st()))
     close(y, ref, 3e-6, "resize_bicubic")
+
+
+# what infer_video_depth's pre-resize sees (video.HipWindowRunner), then the edges of the kernel: all four taps clamped, identity, up-scale
+RESIZE_VIDEO_SHAPES = [
+    (1080, 1920, 518, 924),  # a full-HD frame at image_shape 518 x 518 (lower_bound_size)
+    (1024, 1280, 224, 280),  # the endoscopy frame at the reference's 224 x 280
+    (61, 83, 42, 56),        # odd sizes, no multiple of anything
+    (20, 30, 60, 90),        # 3x up-scale: negative source coordinates at the border
+    (1, 7, 5, 9), (7, 1, 9, 5), (2, 3, 7, 8), (3, 2, 5, 6), (1, 1, 4, 4), (37, 53, 1, 1), (3, 3, 2, 2),  # height / width 1, 2, 3: every tap clamps
+]
+
+
+def _frames_u8(planes, H, W, seed=5):
+    """Values k / 255 in [0, 1], as the runner feeds the kernel (uint8 frames converted on the device)."""
+    return torch.randint(0, 256, (planes, 1, H, W), generator=torch.Generator().manual_seed(seed)).float() / 255.0
+
+
+@pytest.mark.parametrize("H,W,OH,OW", RESIZE_VIDEO_SHAPES)
+def test_resize_bicubic_against_fp64(lib, cuda, H, W, OH, OW):
+    """edv_resize_bicubic against the published algorithm in fp64 (Keys cubic a = -0.75, half-pixel centres, clamped borders, no antialiasing:
+    F.interpolate(bicubic, align_corners=False) on doubles = cv2.INTER_CUBIC on float images), on 8-bit image values.  ATen's own fp32 result
+    is printed beside it: it evaluates the source coordinate in fp32, whose ulp at row 1000 is 6e-5, and ends 1e-4 of the range away from
+    the fp64 result on a full-HD frame; the kernel splits the coordinate in integers and stays at fp32 rounding of the sum at every size."""
+    x = _frames_u8(3, H, W)
+    ref = F.interpolate(x.double(), size=(OH, OW), mode="bicubic", align_corners=False)
+    aten = F.interpolate(x, size=(OH, OW), mode="bicubic", align_corners=False)
+    xd = x.to(cuda)
+    y = torch.full((3, 1, OH, OW), float("nan"), device=cuda)
+    _lib.check(lib.edv_resize_bicubic(xd.data_ptr(), y.data_ptr(), 3, H, W, OH, OW, st()))
+    scale = ref.abs().max().item()
+    err = (y.double().cpu() - ref).abs().max().item() / scale
+    aten_err = (aten.double() - ref).abs().max().item() / scale
+    print(f"\n[resize_bicubic] {H}x{W} -> {OH}x{OW}: scale-relative error {err:.2e} (ATen fp32 {aten_err:.2e})")
+    close(y, ref, 3e-6, "resize_bicubic vs fp64")
+
+
+@pytest.mark.parametrize("H,W", [(224, 280), (42, 56), (1, 1), (3, 5)])
+def test_resize_bicubic_identity_is_exact(lib, cuda, H, W):
+    """Same size in and out: the source coordinate is the pixel itself, the weights are (0, 1, 0, 0), the input comes back bit for bit."""
+    xd = _frames_u8(3, H, W, seed=6).to(cuda)
+    y = torch.full((3, 1, H, W), float("nan"), device=cuda)
+    _lib.check(lib.edv_resize_bicubic(xd.data_ptr(), y.data_ptr(), 3, H, W, H, W, st()))
+    assert torch.equal(y, xd)
 
 
 @pytest.mark.parametrize("dv", [False, True])
