@@ -253,6 +253,16 @@ int edv_resize_bicubic(const float *x_dev, float *y_dev, int32_t planes, int32_t
     return resize_bicubic(x_dev, y_dev, planes, H, W, OH, OW, (hipStream_t)stream);
 }
 
+size_t edv_stitch_workspace(void) { return stitch_workspace(); }
+int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
+                   size_t workspace_bytes, void *stream) {
+    return stitch_fit(disp_dev, ih, iw, tail_dev, fh, fw, st_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+int edv_stitch_apply(const float *disp_dev, int32_t ih, int32_t iw, const float *st_dev, float *tail_dev, float *new_dev, int32_t fh, int32_t fw,
+                     void *stream) {
+    return stitch_apply(disp_dev, ih, iw, st_dev, tail_dev, new_dev, fh, fw, (hipStream_t)stream);
+}
+
 int edv_fold_lora(const float *W_dev, const float *A_dev, const float *B_dev, const float *U_dev, const float *V_dev, float scale, float *out_dev,
                   int32_t nout, int32_t nin, int32_t r, void *stream) {
     return fold_lora(W_dev, A_dev, B_dev, U_dev, V_dev, scale, out_dev, nout, nin, r, (hipStream_t)stream);

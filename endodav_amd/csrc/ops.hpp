@@ -110,6 +110,10 @@ int cls_rows(const float *cls, const float *pos, float *tokens, int F, int ntok,
 int sigmoid_inplace(float *x, long long n, hipStream_t st);
 // planar bicubic image resize (cv2.INTER_CUBIC semantics) for infer_video_depth's pre-resize
 int resize_bicubic(const float *x, float *y, int NP, int H, int W, int OH, int OW, hipStream_t st);
+// whole-video stitching on the device (stitch.hip): disp [32, ih, iw] is upsampled to [fh, fw] on the fly; st = (s, t) in device memory
+size_t stitch_workspace();  // bytes
+int stitch_fit(const float *disp, int ih, int iw, const float *tail, int fh, int fw, float *st, void *ws, size_t ws_bytes, hipStream_t stream);
+int stitch_apply(const float *disp, int ih, int iw, const float *st, float *tail, float *out_new, int fh, int fw, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -14,24 +14,12 @@
 // moves the interpolation weight by up to an ulp of the coordinate (3e-5 at 518 px).  These kernels are
 // HBM-bound, so contraction buys nothing here: switch it off for the whole file.
 #pragma clang fp contract(off)
+#include "resample_coord.hpp"  // lin_coord, lin_ratio, bilinear_tap (shared with stitch.hip)
 
 namespace edv {
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ void lin_coord(int dst, int in, int out, float ratio, int &i0, int &i1, float &l1) {
-    if (in == out) {
-        i0 = i1 = dst;
-        l1 = 0.f;
-        return;
-    }
-    const float src = __fmul_rn(ratio, (float)dst);  // rounded product, as ATen computes it (no FMA into src - i0)
-    i0 = (int)src;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-}
-inline float lin_ratio(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 __global__ __launch_bounds__(256) void patchify_kernel(const float *__restrict__ x, float *__restrict__ cols, int F, int H, int W, int ih, int iw,
                                                         float rh, float rw, int ld) {
@@ -99,10 +87,7 @@ __global__ __launch_bounds__(256) void bilinear_c1_kernel(const float *__restric
         float ly, lx;
         lin_coord(oy, H, OH, rh, y0, y1, ly);
         lin_coord(ox, W, OW, rw, x0, x1, lx);
-        const float *pl = x + f * H * W;
-        const float v00 = pl[(long long)y0 * W + x0], v01 = pl[(long long)y0 * W + x1];
-        const float v10 = pl[(long long)y1 * W + x0], v11 = pl[(long long)y1 * W + x1];
-        y[i] = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+        y[i] = bilinear_tap(x + f * H * W, W, y0, y1, x0, x1, ly, lx);
     }
 }
 

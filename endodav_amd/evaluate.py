@@ -103,14 +103,17 @@ def tas(depth_a, mask_a, i2w_a, depth_b, mask_b, i2w_b) -> float:
 
 
 # ---- harness ---------------------------------------------------------------------------------------------------------
-def _evaluate_clip(depther, item: dict, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device) -> Dict[str, object]:
+def _evaluate_clip(depther, item: dict, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device, stitch=None) -> Dict[str, object]:
     """One clip of evaluate_depth_video.py:163-215: ``infer_video_depth`` -> depth -> alignment -> per-frame errors and
-    frame-to-frame TAE (x100) / TAS."""
+    frame-to-frame TAE (x100) / TAS.  ``stitch`` reaches ``infer_video_depth`` only when it is given: a depther need not know it."""
     MIN_DEPTH = 1e-3
     colors, gts, poses, Ks = item["colors"], item["depths"], item["poses"], item["Ks"]
     rec: Dict[str, object] = {"errors": [], "temporal": [], "ratio": None, "align": None}
     t0 = time.time()
-    disp = depther.infer_video_depth(colors, device=device) if device is not None else depther.infer_video_depth(colors)
+    kw = {} if device is None else {"device": device}
+    if stitch is not None:
+        kw["stitch"] = stitch
+    disp = depther.infer_video_depth(colors, **kw)
     rec["time"] = time.time() - t0
     _, pred = disp_to_depth(disp, min_depth, max_depth)
     if depth_align == "scale":
@@ -136,8 +139,9 @@ def _evaluate_clip(depther, item: dict, min_depth, max_depth, depth_align, pred_
 
 def evaluate_video(depther, dataset: Iterable[dict], *, min_depth: float = 0.1, max_depth: float = 150.0, depth_align: str = "scale",
                    pred_depth_scale_factor: float = 1.0, eval_max_depth: float = 150.0, device: str = "cuda",
-                   rank: Optional[int] = None, world: Optional[int] = None) -> Optional[Dict[str, object]]:
-    """The loop of evaluate_depth_video.py:163-215.  ``depther`` only needs ``infer_video_depth(colors)``.
+                   rank: Optional[int] = None, world: Optional[int] = None, stitch: Optional[str] = None) -> Optional[Dict[str, object]]:
+    """The loop of evaluate_depth_video.py:163-215.  ``depther`` only needs ``infer_video_depth(colors)``; ``stitch`` ("host" / "device",
+    ``video.infer_video_depth``) is handed to it only when given.
 
     Clips are independent units: with ``world`` > 1 (default: the ``torch.distributed`` process group, if any) rank r
     evaluates clips r, r + world, ... on its own GPU -- indexed directly when the dataset supports ``len`` / ``[]`` (the reference's
@@ -147,7 +151,7 @@ def evaluate_video(depther, dataset: Iterable[dict], *, min_depth: float = 0.1, 
 
     if rank is None or world is None:
         rank, world = parallel.rank_world()
-    args = (min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device)
+    args = (min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device, stitch)
     indexable = hasattr(dataset, "__getitem__") and hasattr(dataset, "__len__")
     if indexable:
         n_clips = len(dataset)

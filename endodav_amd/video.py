@@ -9,7 +9,9 @@ Differences in *where* work happens, not in what is computed:
     ``edv_bilinear`` and come back in ONE device→host copy instead of 32, behind the next window's forward;
   - the windows of one video are independent given the input frames (``window_sources``) and can be sharded over ranks
     (``shard_windows=True``, opt-in);
-  - the least-squares scale/shift and the cross-fade run in numpy float32 exactly as the reference's.
+  - the least-squares scale/shift and the cross-fade run in numpy float32 exactly as the reference's (``stitch="host"``, the default), or
+    on the GPU with fp64 sums, fused with the resize back to the frame size (``stitch="device"``, opt-in: ``edv_stitch_fit`` /
+    ``edv_stitch_apply``, tests/test_stitch_gpu.py).
 
 The cv2.INTER_CUBIC pre-resize is "parity unpinned" (cv2 is absent from the build
 container and the reference has no fixture for it); the kernel implements the published algorithm
@@ -134,14 +136,15 @@ class HipWindowRunner:
         ih, iw = model.image_shape
         self.tw, self.th = lower_bound_size(self.fw, self.fh, iw, ih)
 
-    def run(self, sources: Sequence[np.ndarray]) -> List[np.ndarray]:
+    def _run_windows(self, sources: Sequence[np.ndarray], begin, before_forward, after_forward) -> None:
+        """The part both stitch paths share: upload, conversion, pre-resize and forward of every window, on the copy-in stream and the lanes.
+        ``begin(nbuf, entry)`` allocates the caller's buffers (``nbuf`` slots are in use at a time; ``entry``: see the stream contract below),
+        ``before_forward(k, slot)`` runs on the host before window k is enqueued, ``after_forward(k, slot, stream, disp)`` under the lane's
+        stream right after its forward: ``disp`` [32, 1, ih, iw] is the window's network-size disparity, valid in stream order."""
         from .pipeline import ClipsInFlight
 
         lib = _lib.load()
         dev, fh, fw, th, tw = self.dev, self.fh, self.fw, self.th, self.tw
-        if not sources:
-            return []
-        results: List[np.ndarray] = []
         with torch.cuda.device(dev), torch.no_grad():
             # Round 3: consecutive windows are independent (window_sources), so up to `depth` of them are in flight on the GPU, each on its own
             # engine context and stream (pipeline.ClipsInFlight; depth by auto_depth: 3 lanes at the reference's 224 x 280, one at 518 x 518 where a
@@ -160,22 +163,20 @@ class HipWindowRunner:
                 except Exception:
                     pass
             nbuf = min(depth + 1, len(sources))
-            s_in, s_out = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+            s_in = torch.cuda.Stream(device=dev)
             s_dash = torch.cuda.Stream(device=dev) if dash else None
             # Stream contract: run() orders itself after everything the caller has enqueued on its current stream so far -- an optimizer.step() or
             # load_state_dict whose weights the first forward on a lane folds and packs, and earlier users of the memory the buffers below get
             # from that stream's allocator pool, which are first written on the streams of this runner.  The copy-in stream and every lane wait
-            # for this event once; the copy-out stream follows the lanes.  All work is drained before run() returns host arrays.
+            # for this event once; the copy-out stream (the stitch stream) follows the lanes.  All work is drained before run() returns host arrays.
             entry = torch.cuda.Event()
             entry.record(torch.cuda.current_stream(dev))
             s_in.wait_event(entry)
             h_in = [torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8).pin_memory() for _ in range(nbuf)]
             d_in = [torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
-            h_out = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32).pin_memory() for _ in range(nbuf)]
-            d_out = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+            begin(nbuf, entry)
             up_done: List[Optional[torch.cuda.Event]] = [None] * nbuf     # H2D of the slot finished (host buffer reusable, device buffer valid)
             used: List[Optional[torch.cuda.Event]] = [None] * nbuf        # the conversion that read d_in[slot] finished (device buffer reusable)
-            out_done: List[Optional[torch.cuda.Event]] = [None] * nbuf    # D2H of the slot finished
 
             def upload(k: int) -> None:
                 slot = k % nbuf
@@ -189,18 +190,12 @@ class HipWindowRunner:
                     up_done[slot] = torch.cuda.Event()
                     up_done[slot].record(s_in)
 
-            def drain(slot: int) -> None:
-                if out_done[slot] is not None:
-                    out_done[slot].synchronize()
-                    results.append(h_out[slot].numpy().copy())
-                    out_done[slot] = None
-
             upload(0)
             for k in range(len(sources)):
                 slot = k % nbuf
                 if k + 1 < len(sources):
                     upload(k + 1)                     # overlaps the windows in flight
-                drain(slot)                           # frees d_out[slot] / h_out[slot] (window k - nbuf's copy), in window order
+                before_forward(k, slot)
                 stream, lane = (s_dash, 0) if dash else flight.next_lane(INFER_LEN)
                 if k < depth:
                     stream.wait_event(entry)          # the lanes come round-robin: the first `depth` windows reach each of them once
@@ -215,18 +210,116 @@ class HipWindowRunner:
                         _lib.check(lib.edv_resize_bicubic(cur.data_ptr(), small.data_ptr(), INFER_LEN * 3, fh, fw, th, tw, st), "edv_resize_bicubic")
                         cur = small
                     disp = self.model(cur.unsqueeze(0), lane=lane)[("disp", 0)]  # [32, 1, ih, iw]
-                    full = d_out[slot]
-                    _lib.check(lib.edv_bilinear(disp.data_ptr(), full.data_ptr(), INFER_LEN, disp.shape[-2], disp.shape[-1], 1, fh, fw, st), "edv_bilinear")
-                    ready = torch.cuda.Event()
-                    ready.record(stream)
-                with torch.cuda.stream(s_out):
-                    s_out.wait_event(ready)
-                    h_out[slot].copy_(full, non_blocking=True)
-                    out_done[slot] = torch.cuda.Event()
-                    out_done[slot].record(s_out)
-            for k in range(max(len(sources) - nbuf, 0), len(sources)):  # in window order: oldest slot first
-                drain(k % nbuf)
+                    after_forward(k, slot, stream, disp)
+
+    def run(self, sources: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """The frame-size maps [32, fh, fw] of the given windows, in the order given (``stitch="host"``, and one rank's share of
+        ``shard_windows=True``): edv_bilinear on the lane, one device->host copy per window on the copy-out stream."""
+        lib = _lib.load()
+        dev, fh, fw = self.dev, self.fh, self.fw
+        if not sources:
+            return []
+        results: List[np.ndarray] = []
+        h_out: List[torch.Tensor] = []
+        d_out: List[torch.Tensor] = []
+        out_done: List[Optional[torch.cuda.Event]] = []                   # D2H of the slot finished
+        s_out = torch.cuda.Stream(device=dev)
+
+        def begin(nbuf: int, entry: torch.cuda.Event) -> None:
+            h_out.extend(torch.empty((INFER_LEN, fh, fw), dtype=torch.float32).pin_memory() for _ in range(nbuf))
+            d_out.extend(torch.empty((INFER_LEN, fh, fw), dtype=torch.float32, device=dev) for _ in range(nbuf))
+            out_done.extend([None] * nbuf)
+
+        def drain(slot: int) -> None:
+            if out_done[slot] is not None:
+                out_done[slot].synchronize()
+                results.append(h_out[slot].numpy().copy())
+                out_done[slot] = None
+
+        def before_forward(k: int, slot: int) -> None:
+            drain(slot)                               # frees d_out[slot] / h_out[slot] (window k - nbuf's copy), in window order
+
+        def after_forward(k: int, slot: int, stream: torch.cuda.Stream, disp: torch.Tensor) -> None:
+            full = d_out[slot]
+            st = C.c_void_p(_lib.stream_ptr(dev))
+            _lib.check(lib.edv_bilinear(disp.data_ptr(), full.data_ptr(), INFER_LEN, disp.shape[-2], disp.shape[-1], 1, fh, fw, st), "edv_bilinear")
+            ready = torch.cuda.Event()
+            ready.record(stream)
+            with torch.cuda.stream(s_out):
+                s_out.wait_event(ready)
+                h_out[slot].copy_(full, non_blocking=True)
+                out_done[slot] = torch.cuda.Event()
+                out_done[slot].record(s_out)
+
+        self._run_windows(sources, begin, before_forward, after_forward)
+        nbuf = len(h_out)
+        for k in range(max(len(sources) - nbuf, 0), len(sources)):  # in window order: oldest slot first
+            drain(k % nbuf)
         return results
+
+    def run_stitched(self, sources: Sequence[np.ndarray], n_keep: int) -> np.ndarray:
+        """``stitch="device"``: all windows of the video (``window_sources``) -> the stitched result [n_keep, fh, fw], float32, in pinned host memory.
+
+        The windows run as in ``run``.  One more stream, the stitch stream, takes the lanes' ``ready`` events in window order and, for window k,
+        fits (s, t) against the 8-frame tail of the output so far (edv_stitch_fit; k >= 1), writes the window's new frames and cross-fades the
+        tail in place (edv_stitch_apply), and copies the frames that became final straight into the result: after window k the output has
+        32 + 22 k frames of which all but the last 8 are final.  Both kernels upsample the network-size disparity on the fly, so the 32
+        frame-size maps of a window exist nowhere; two frame-size buffers [32, fh, fw] alternate between the windows (the tail is the end of the
+        previous window's buffer), whatever the length of the video.  Padding frames beyond ``n_keep`` are computed and never copied.
+        A window's disparity is a tensor of the lane's allocator pool: ``record_stream`` keeps its memory from being handed out again before
+        the stitch stream has read it."""
+        lib = _lib.load()
+        dev, fh, fw = self.dev, self.fh, self.fw
+        step = INFER_LEN - OVERLAP
+        last = len(sources) - 1
+        if last < 0:
+            return np.empty((0, fh, fw), dtype=np.float32)
+        s_st = torch.cuda.Stream(device=dev)
+        state: dict = {"done": 0}
+
+        def begin(nbuf: int, entry: torch.cuda.Event) -> None:
+            s_st.wait_event(entry)
+            state["ring"] = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32, device=dev) for _ in range(min(2, len(sources)))]
+            state["st"] = torch.empty(2, dtype=torch.float32, device=dev)
+            state["ws"] = torch.empty(int(lib.edv_stitch_workspace()), dtype=torch.uint8, device=dev)
+            state["out"] = torch.empty((n_keep, fh, fw), dtype=torch.float32, pin_memory=True)
+
+        def place(g: int) -> Tuple[int, int]:
+            """(window, index in that window's buffer) of output frame g: window 0 holds frames 0..31, window k >= 1 frames 22 k + 10 .. 22 k + 31."""
+            return (0, g) if g < INFER_LEN else ((g - OVERLAP) // step, (g - OVERLAP) % step)
+
+        def after_forward(k: int, slot: int, stream: torch.cuda.Stream, disp: torch.Tensor) -> None:
+            ring, out = state["ring"], state["out"]
+            ready = torch.cuda.Event()
+            ready.record(stream)
+            with torch.cuda.stream(s_st):
+                s_st.wait_event(ready)
+                st = C.c_void_p(s_st.cuda_stream)
+                disp = disp.contiguous()
+                ih, iw = disp.shape[-2], disp.shape[-1]
+                cur = ring[k % 2]
+                if k == 0:
+                    _lib.check(lib.edv_stitch_apply(disp.data_ptr(), ih, iw, None, None, cur.data_ptr(), fh, fw, st), "edv_stitch_apply")
+                else:
+                    tail = ring[(k - 1) % 2][(INFER_LEN if k == 1 else step) - INTERP_LEN:]
+                    _lib.check(lib.edv_stitch_fit(disp.data_ptr(), ih, iw, tail.data_ptr(), fh, fw, state["st"].data_ptr(), state["ws"].data_ptr(),
+                                                  state["ws"].numel(), st), "edv_stitch_fit")
+                    _lib.check(lib.edv_stitch_apply(disp.data_ptr(), ih, iw, state["st"].data_ptr(), tail.data_ptr(), cur.data_ptr(), fh, fw, st),
+                               "edv_stitch_apply")
+                disp.record_stream(s_st)
+                upto = n_keep if k == last else min(n_keep, INFER_LEN + step * k - INTERP_LEN)
+                g = state["done"]
+                while g < upto:                       # at most two pieces: the faded tail in window k-1's buffer, then window k's own frames
+                    w, i = place(g)
+                    cnt = min(upto - g, (INFER_LEN if w == 0 else step) - i)
+                    out[g:g + cnt].copy_(ring[w % 2][i:i + cnt], non_blocking=True)
+                    g += cnt
+                state["done"] = max(state["done"], upto)
+
+        self._run_windows(sources, begin, lambda k, slot: None, after_forward)
+        s_st.synchronize()
+        assert state["done"] == n_keep
+        return state["out"].numpy()
 
     def resized_clip(self, source: np.ndarray) -> torch.Tensor:
         """The network input of one window, [1, 32, 3, th, tw] on the device (what ``run`` feeds the forward): for tests."""
@@ -242,7 +335,7 @@ class HipWindowRunner:
 
 
 # ---------------------------------------------------------------------------------------------
-def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None, shard_windows=False, rank=None, world=None):
+def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None, shard_windows=False, rank=None, world=None, stitch="host"):
     """endodav.infer_video_depth (endodav.py:162-254).  By default every window of the video runs on the calling rank, whatever process group
     exists: that is what ``evaluate.evaluate_video`` needs, where each rank already holds a DIFFERENT clip (sharding the windows of those clips
     over the same ranks would pair up collectives of different clips -- ADVICE round 2).
@@ -252,9 +345,20 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
     gathers the per-window maps, stitches them in window order and returns the result; the other ranks return None.  ``rank`` / ``world``
     default to the process group's.  No data-path collective besides that gather.
 
-    ``runner``: anything with ``run(sources) -> [np.ndarray [32, H, W]]`` (default ``HipWindowRunner``; the gloo tests pass a stub)."""
+    ``stitch``: ``"host"`` (default) aligns and cross-fades the windows in numpy float32 exactly as the reference does (``stitch_windows``);
+    ``"device"`` (opt-in) does both on the GPU, window by window behind the forwards, and copies every frame to the host once
+    (``HipWindowRunner.run_stitched``).  The device path sums in fp64, so it is closer to exact arithmetic than the reference's float32 solve;
+    the two agree to about 1e-6 of the output's scale on well-conditioned clips and are not bit-identical.  Its result lies in pinned host
+    memory.  It does not combine with ``shard_windows=True``, which stitches on the host of rank 0.
+
+    ``runner``: anything with ``run(sources) -> [np.ndarray [32, H, W]]`` (default ``HipWindowRunner``; the gloo tests pass a stub);
+    ``stitch="device"`` needs its ``run_stitched(sources, n) -> np.ndarray [n, H, W]`` as well."""
     from . import parallel
 
+    if stitch not in ("host", "device"):
+        raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
+    if stitch == "device" and shard_windows:
+        raise ValueError("stitch='device' does not combine with shard_windows=True: sharded windows are gathered and stitched on the host of rank 0")
     frames = np.asarray(frames)
     if frames.ndim != 4 or frames.shape[-1] != 3:
         raise ValueError(f"expected frames [N, H, W, 3], got {frames.shape}")
@@ -265,6 +369,8 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
             raise RuntimeError("infer_video_depth runs on MI355X only (device must be a CUDA/ROCm device)")
         runner = HipWindowRunner(model, np.ascontiguousarray(frames), dev)
     sources = window_sources(n)
+    if stitch == "device":
+        return runner.run_stitched(sources, n)
     if not shard_windows:
         return stitch_windows(runner.run(sources), n)
     if rank is None or world is None:

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define EDV_ABI_VERSION 11 /* 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
+#define EDV_ABI_VERSION 12 /* 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
 
 enum edv_lora_type { EDV_LORA_NONE = 0, EDV_LORA_LORA = 1, EDV_LORA_DVLORA = 2, EDV_LORA_SSB = 3, EDV_LORA_DASH = 4 };
 
@@ -253,6 +253,22 @@ int edv_bicubic_pos(const float *grid_dev, float *out_dev, int32_t S, int32_t D,
 /* Bicubic resize of `planes` images [H,W] -> [OH,OW] (Keys cubic a=-0.75, half-pixel centres, clamped
  * borders = cv2.INTER_CUBIC): the frame pre-resize of infer_video_depth (endodav.py:170-181,196). */
 int edv_resize_bicubic(const float *x_dev, float *y_dev, int32_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, void *stream);
+
+/* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
+ * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
+ * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
+ * edv_stitch_fit: least-squares (s, t) with s*p + t ~ tail over the 8 overlap pairs (window slots 2..9 against tail_dev [8, fh, fw], the
+ * already aligned last 8 frames of the output so far).  Sums and the 2x2 solve in fp64, reduced in a fixed order (same input, same bits);
+ * det == 0 gives (1, 0).  st_dev [2] receives (s, t) rounded to fp32; nothing comes back to the host.
+ * edv_stitch_apply: reads (s, t) from st_dev; writes max(p*s + t, 0) of slots 10..31 to new_dev [22, fh, fw] and the cross-fade
+ * pre*(1 - f_i) + max(p*s + t, 0)*f_i of slots 2..9 in place over tail_dev (f_i = 0, 1/7, ..., 1 rounded to fp32).  Window 0:
+ * st_dev = tail_dev = NULL, new_dev [32, fh, fw] receives the plain upsample of all 32 slots (no clamp).
+ * 16-byte accesses when fh*fw is a multiple of 4 and tail_dev / new_dev are 16-byte aligned, one pixel per access otherwise. */
+size_t edv_stitch_workspace(void); /* bytes; the same for every size */
+int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
+                   size_t workspace_bytes, void *stream);
+int edv_stitch_apply(const float *disp_dev, int32_t ih, int32_t iw, const float *st_dev, float *tail_dev, float *new_dev, int32_t fh, int32_t fw,
+                     void *stream);
 
 /* out = W + scale * (B∘V)(A∘U)  (U, V may be NULL): the LoRA / DV-LoRA fold of mylora/layers.py:148-157,384-393. */
 int edv_fold_lora(const float *W_dev, const float *A_dev, const float *B_dev, const float *U_dev, const float *V_dev, float scale, float *out_dev,
