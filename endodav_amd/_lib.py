@@ -11,7 +11,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EDV_LIB_PATH") or os.path.join(_HERE, "lib", "libendodav_hip.so")  # override: experiments only
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 LORA_TYPES = {"none": 0, "lora": 1, "dvlora": 2, "ssb": 3, "dash": 4}
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_SIGMOID_NEG = 0, 1, 2, 3, 4
@@ -139,6 +139,17 @@ SIGNATURES = {
     "edv_photometric_loss": (C.c_int, [_fp, C.POINTER(C.c_void_p), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _f32, _f32, _f32,
                                        _fp, C.POINTER(C.c_void_p), _fp, C.c_size_t, C.c_void_p]),
     "edv_fold_lora": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _f32, _fp, _i32, _i32, _i32, C.c_void_p]),
+    # test entry points (ABI 13); a row map is int32[4] = (period, stride, offset, inner), NULL = identity
+    "edv_gemm_desc": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "edv_layernorm_mapped": (C.c_int, [_fp, C.POINTER(_i32), _fp, _fp, _fp, C.POINTER(_i32), _i64, _i32, _f32, _fp, _i32, _i32, _i32, _i32, C.c_void_p]),
+    "edv_layernorm_bwd_mapped": (C.c_int, [_fp, C.POINTER(_i32), _fp, _fp, C.POINTER(_i32), _fp, C.POINTER(_i32), _i64, _i32, _f32, _i32, C.c_void_p]),
+    "edv_fold_ssb": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),
+    "edv_fold_bn": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _f32, _fp, _i32, _i32, C.c_void_p]),
+    "edv_fold_dash": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, C.c_void_p]),
+    "edv_col_dot": (C.c_int, [_fp, _fp, _i64, _i32, _fp, _fp, _fp, C.c_void_p]),
+    "edv_ssb_prep": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),
+    "edv_sigmoid_bwd": (C.c_int, [_fp, _fp, _fp, _i64, C.c_void_p]),
+    "edv_bilinear_add": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]),
 }
 
 
@@ -204,6 +215,14 @@ class TrainerLossWeights(C.Structure):
 class TrainerLossGrads(C.Structure):
     _fields_ = [("disp", C.c_void_p * 4), ("refined", (C.c_void_p * 2) * 4), ("transform", (C.c_void_p * 2) * 4), ("K", C.c_void_p), ("invK", C.c_void_p),
                 ("T", C.c_void_p * 2)]
+
+
+class GemmDescC(C.Structure):
+    """edv_gemm_desc_t (include/endodav_hip.h): the GEMM descriptor of the test entry point edv_gemm_desc."""
+    _fields_ = [("A", C.c_void_p), ("lda", _i32), ("a_map", _i32 * 4), ("W", C.c_void_p), ("ldw", _i32), ("C", C.c_void_p), ("ldc", _i32), ("c_map", _i32 * 4),
+                ("M", _i64), ("N", _i32), ("K", _i32), ("bias", C.c_void_p), ("act", _i32), ("gamma", C.c_void_p), ("R1", C.c_void_p), ("ldr1", _i32),
+                ("r1_map", _i32 * 4), ("R2", C.c_void_p), ("ldr2", _i32), ("P1", C.c_void_p), ("ldp1", _i32), ("p1_map", _i32 * 4), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("x6_planes", C.c_void_p)]
 
 
 def stream_ptr(device=None) -> int:

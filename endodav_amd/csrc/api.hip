@@ -268,6 +268,80 @@ int edv_fold_lora(const float *W_dev, const float *A_dev, const float *B_dev, co
     return fold_lora(W_dev, A_dev, B_dev, U_dev, V_dev, scale, out_dev, nout, nin, r, (hipStream_t)stream);
 }
 
+// ---- test entry points (ABI 13): the descriptor forms only the engine reaches otherwise (tests/test_mapped_kernels_gpu.py) ----
+namespace edv {
+namespace {
+// (period, stride, offset, inner) -> RowMap; a null pointer is the identity
+bool row_map_from(const int32_t *m, RowMap *out) {
+    *out = identity_map();
+    if (!m) return true;
+    if (m[0] < 0 || m[1] < 0 || m[2] < 0 || (m[3] != 0 && m[3] != 1)) return false;
+    *out = RowMap{m[0], m[1], m[2], m[3]};
+    return true;
+}
+}  // namespace
+}  // namespace edv
+
+int edv_gemm_desc(const edv_gemm_desc_t *d, void *stream) {
+    EDV_CHECK(d, "null descriptor");
+    GemmDesc g;
+    g.A = d->A; g.lda = d->lda; g.W = d->W; g.ldw = d->ldw; g.C = d->C; g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.K = d->K;
+    g.bias = d->bias; g.act = d->act; g.gamma = d->gamma;
+    g.R1 = d->R1; g.ldr1 = d->ldr1; g.R2 = d->R2; g.ldr2 = d->ldr2; g.P1 = d->P1; g.ldp1 = d->ldp1;
+    g.ws = d->workspace; g.ws_floats = d->workspace_bytes / sizeof(float);
+    g.Wx6 = d->x6_planes;
+    EDV_CHECK(row_map_from(d->a_map, &g.a_map) && row_map_from(d->c_map, &g.c_map) && row_map_from(d->r1_map, &g.r1_map) &&
+                  row_map_from(d->p1_map, &g.p1_map),
+              "row map: period, stride, offset >= 0 and inner 0 or 1");
+    EDV_CHECK(d->act >= ACT_NONE && d->act <= ACT_RELU, "act must be 0, 1 or 2");
+    EDV_CHECK(d->N > 0 && d->ldc >= d->N, "ldc must be at least N");
+    EDV_CHECK(!d->R1 || d->ldr1 >= d->N, "ldr1 must be at least N");
+    EDV_CHECK(!d->R2 || d->ldr2 >= d->N, "ldr2 must be at least N");
+    EDV_CHECK(!d->P1 || d->ldp1 >= d->N, "ldp1 must be at least N");
+    return gemm(g, (hipStream_t)stream);
+}
+
+int edv_layernorm_mapped(const float *x_dev, const int32_t *in_map, const float *w_dev, const float *b_dev, float *y_dev, const int32_t *out_map,
+                         int64_t rows, int32_t dim, float eps, const float *pe_dev, int32_t rows_per_frame, int32_t T, int32_t act, int32_t accumulate,
+                         void *stream) {
+    RowMap im, om;
+    EDV_CHECK(row_map_from(in_map, &im) && row_map_from(out_map, &om), "row map: period, stride, offset >= 0 and inner 0 or 1");
+    return layernorm(x_dev, im, w_dev, b_dev, y_dev, om, rows, dim, eps, pe_dev, rows_per_frame, T, (hipStream_t)stream, act, accumulate != 0);
+}
+
+int edv_layernorm_bwd_mapped(const float *x_dev, const int32_t *x_map, const float *w_dev, const float *dy_dev, const int32_t *dy_map, float *dx_dev,
+                             const int32_t *dx_map, int64_t rows, int32_t dim, float eps, int32_t accumulate, void *stream) {
+    RowMap xm, gm, dm;
+    EDV_CHECK(row_map_from(x_map, &xm) && row_map_from(dy_map, &gm) && row_map_from(dx_map, &dm), "row map: period, stride, offset >= 0 and inner 0 or 1");
+    return layernorm_bwd(x_dev, xm, w_dev, dy_dev, gm, dx_dev, dm, rows, dim, eps, accumulate != 0, (hipStream_t)stream);
+}
+
+int edv_fold_ssb(const float *W_dev, const float *a_dev, const float *b_dev, float *out_dev, int32_t nout, int32_t nin, void *stream) {
+    return fold_ssb(W_dev, a_dev, b_dev, out_dev, nout, nin, (hipStream_t)stream);
+}
+int edv_fold_bn(float *w_dev, const float *b_dev, const float *gamma_dev, const float *beta_dev, const float *mean_dev, const float *var_dev, float eps,
+                float *bout_dev, int32_t nout, int32_t K, void *stream) {
+    return fold_bn(w_dev, b_dev, gamma_dev, beta_dev, mean_dev, var_dev, eps, bout_dev, nout, K, (hipStream_t)stream);
+}
+int edv_fold_dash(const float *Utop_dev, const float *idx_dev, const float *Vtop_dev, float *inout_dev, int32_t nout, int32_t nin, int32_t r, void *stream) {
+    return fold_dash(Utop_dev, idx_dev, Vtop_dev, inout_dev, nout, nin, r, (hipStream_t)stream);
+}
+int edv_col_dot(const float *P_dev, const float *Q_dev, int64_t M, int32_t N, const float *scale_dev, float *part_dev, float *out_dev, void *stream) {
+    return col_dot(P_dev, Q_dev, M, N, scale_dev, part_dev, out_dev, (hipStream_t)stream);
+}
+int edv_ssb_prep(const float *W_dev, const float *a_dev, const float *b_dev, const float *gamma_dev, float *Wa_dev, float *gb_dev, int32_t nout,
+                 int32_t nin, void *stream) {
+    return ssb_prep(W_dev, a_dev, b_dev, gamma_dev, Wa_dev, gb_dev, nout, nin, (hipStream_t)stream);
+}
+int edv_sigmoid_bwd(const float *g_dev, const float *s_dev, float *out_dev, int64_t n, void *stream) {
+    return sigmoid_bwd(g_dev, s_dev, out_dev, n, (hipStream_t)stream);
+}
+int edv_bilinear_add(const float *x_dev, const float *add_dev, float *y_dev, int32_t F, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
+                     void *stream) {
+    EDV_CHECK(add_dev, "null addend");
+    return bilinear(x_dev, y_dev, F, H, W, C, OH, OW, ACT_NONE, (hipStream_t)stream, add_dev);
+}
+
 size_t edv_trainer_loss_workspace(int32_t N, int32_t H, int32_t W) { return trainer_loss_workspace(N, H, W) * sizeof(float); }
 int edv_trainer_loss(const edv_trainer_loss_inputs *in, int32_t N, int32_t H, int32_t W, const edv_trainer_loss_weights *weights, float *losses_dev,
                      const edv_trainer_loss_grads *grads, float *workspace_dev, size_t workspace_bytes, void *stream) {

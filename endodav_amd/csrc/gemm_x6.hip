@@ -442,7 +442,10 @@ int gemm_x6_split(const float *W, void *planes, int N, int K, hipStream_t st) {
 }
 
 bool gemm_x6_supported(const GemmDesc &d) {
-    const int ek = epilogue_kind(d);  // 1 + ACT: identity row maps, no pre-activation addend, a compile-time activation
+    const int ek = epilogue_kind(d);  // 1 + ACT: identity row maps on C / R1, no pre-activation addend, a compile-time activation
+    // epilogue_kind does not look at the A operand: a row map on A (the tap projection's form) stays with the fp32 kernels, as the contract
+    // in gemm_x6()'s message says -- no caller combines planes with one, and nothing tests this kernel's loader with one
+    if (d.a_map.period != 0) return false;
     if (!(d.Wx6 && d.loader == LOAD_DENSE && ek >= 1 && ek <= 3 && d.K % XBK == 0 && d.lda % 4 == 0 && d.ldw == d.K && d.M > 0 && d.N >= 64)) return false;
     if (!((long long)3 * d.N * d.K * 2 < (1ll << 32) - (1 << 20))) return false;  // the planes behind one buffer descriptor
     // the buffer epilogue's 32-bit offsets and descriptor masking (see fits_buffer in gemm_dma.hip): a tile's rows run up to 127 past M

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define EDV_ABI_VERSION 12 /* 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
+#define EDV_ABI_VERSION 13 /* 13: test entry points for row-mapped GEMM / LayerNorm descriptors and the folds (edv_gemm_desc ... edv_bilinear_add); 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
 
 enum edv_lora_type { EDV_LORA_NONE = 0, EDV_LORA_LORA = 1, EDV_LORA_DVLORA = 2, EDV_LORA_SSB = 3, EDV_LORA_DASH = 4 };
 
@@ -436,6 +436,67 @@ int edv_conv3x3_s2_bwd(const float *dy_dev, const float *wpacked_dev, float *dx_
 int edv_dilate2(const float *dy_dev, float *z_dev, int32_t F, int32_t H, int32_t W, int32_t C, void *stream);
 /* ConvTranspose(k = s) input gradient = edv_gemm of the pixel-unshuffled dy [F*h*w, s*s*C] with the transposed packed weight. */
 int edv_pixel_unshuffle(const float *dy_dev, float *A_dev, int32_t F, int32_t h, int32_t w, int32_t C, int32_t s, void *stream);
+
+/* ---- test entry points (ABI 13): the operator forms only the engine used to reach.  No reference counterpart. ----
+ * A row map is int32_t[4] = (period, stride, offset, inner): logical row m lives at physical row
+ *   (m / period) * stride + offset + inner * (m % period);   period 0 (or a NULL map pointer) = identity.
+ * stride 0 broadcasts one block over the frames, inner 0 one row per frame over that frame's rows. */
+typedef struct edv_gemm_desc_t {
+    const float *A;            /* [rows, lda], logical row m read at a_map(m) */
+    int32_t lda;
+    int32_t a_map[4];
+    const float *W;            /* [N, ldw] (torch Linear layout); may point into a wider matrix */
+    int32_t ldw;
+    float *C;                  /* logical row m stored at c_map(m), columns 0..N-1 of a row of ldc floats */
+    int32_t ldc;
+    int32_t c_map[4];
+    int64_t M;
+    int32_t N, K;
+    const float *bias;         /* [N] or NULL */
+    int32_t act;               /* 0 none, 1 GELU, 2 ReLU */
+    const float *gamma;        /* [N] or NULL */
+    const float *R1;           /* residual read at r1_map(m), or NULL; may alias C */
+    int32_t ldr1;
+    int32_t r1_map[4];
+    const float *R2;           /* second residual, read at the OUTPUT row c_map(m), or NULL */
+    int32_t ldr2;
+    const float *P1;           /* pre-activation addend read at p1_map(m), or NULL */
+    int32_t ldp1;
+    int32_t p1_map[4];
+    float *workspace;          /* stream-K workspace (edv_gemm_workspace bytes) or NULL: plain grid */
+    size_t workspace_bytes;
+    const void *x6_planes;     /* bf16 planes of W (edv_gemm_x6_split) or NULL; used only where the bf16x6 kernel supports the descriptor */
+} edv_gemm_desc_t;
+/* C = epilogue(A W^T) through the same dispatcher the engine calls, dense loader and row store:
+ *   v = acc + bias[n] + P1[p1_map(m), n];  v = act(v) * gamma[n];  v += R1[r1_map(m), n] + R2[c_map(m), n].
+ * Refuses ldc / ldr1 / ldr2 / ldp1 < N, a map with period < 0, stride < 0, offset < 0 or inner outside {0, 1}, act outside 0..2. */
+int edv_gemm_desc(const edv_gemm_desc_t *d, void *stream);
+/* edv_layernorm with row maps (NULL = identity), an output activation (0 none, 1 GELU) and y += instead of y =. */
+int edv_layernorm_mapped(const float *x_dev, const int32_t *in_map, const float *w_dev, const float *b_dev, float *y_dev, const int32_t *out_map,
+                         int64_t rows, int32_t dim, float eps, const float *pe_dev, int32_t rows_per_frame, int32_t T, int32_t act, int32_t accumulate,
+                         void *stream);
+/* edv_layernorm_bwd with row maps on x, dy and dx (NULL = identity). */
+int edv_layernorm_bwd_mapped(const float *x_dev, const int32_t *x_map, const float *w_dev, const float *dy_dev, const int32_t *dy_map, float *dx_dev,
+                             const int32_t *dx_map, int64_t rows, int32_t dim, float eps, int32_t accumulate, void *stream);
+/* Linear_SSB fold: out[n, k] = a[k] * W[n, k] * b[n]. */
+int edv_fold_ssb(const float *W_dev, const float *a_dev, const float *b_dev, float *out_dev, int32_t nout, int32_t nin, void *stream);
+/* Eval-mode BatchNorm folded into the preceding convolution, in place: w[n, :] *= s[n], bout[n] = (b[n] - mean[n]) * s[n] + beta[n],
+ * s = gamma / sqrt(var + eps). */
+int edv_fold_bn(float *w_dev, const float *b_dev, const float *gamma_dev, const float *beta_dev, const float *mean_dev, const float *var_dev, float eps,
+                float *bout_dev, int32_t nout, int32_t K, void *stream);
+/* DashLinear after warm-up, in place: inout += Utop [nout, r] diag(idx [r]) Vtop [r, nin]. */
+int edv_fold_dash(const float *Utop_dev, const float *idx_dev, const float *Vtop_dev, float *inout_dev, int32_t nout, int32_t nin, int32_t r, void *stream);
+/* out[n] = scale[n] * sum_m P[m, n] * Q[m, n]  (Q NULL: column sums of P; scale NULL: 1); part_dev: 64 * N floats of scratch.
+ * Fixed summation order: bit-reproducible. */
+int edv_col_dot(const float *P_dev, const float *Q_dev, int64_t M, int32_t N, const float *scale_dev, float *part_dev, float *out_dev, void *stream);
+/* Linear_SSB backward preparation: Wa[n, k] = W[n, k] * a[k], gb[n] = b[n] * gamma[n] (gamma NULL: 1). */
+int edv_ssb_prep(const float *W_dev, const float *a_dev, const float *b_dev, const float *gamma_dev, float *Wa_dev, float *gb_dev, int32_t nout,
+                 int32_t nin, void *stream);
+/* out = g * s * (1 - s), s = the sigmoid's output; any n. */
+int edv_sigmoid_bwd(const float *g_dev, const float *s_dev, float *out_dev, int64_t n, void *stream);
+/* edv_bilinear plus an addend shaped like the output (C % 4 == 0): y = up(x) + add. */
+int edv_bilinear_add(const float *x_dev, const float *add_dev, float *y_dev, int32_t F, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
+                     void *stream);
 
 #ifdef __cplusplus
 }
