@@ -11,7 +11,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EDV_LIB_PATH") or os.path.join(_HERE, "lib", "libendodav_hip.so")  # override: experiments only
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 LORA_TYPES = {"none": 0, "lora": 1, "dvlora": 2, "ssb": 3, "dash": 4}
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_SIGMOID_NEG = 0, 1, 2, 3, 4
@@ -135,6 +135,12 @@ SIGNATURES = {
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),
+    # evaluation on the device (ABI 14); results and scalars are doubles in device memory
+    "edv_metrics_workspace": (C.c_size_t, [_i64, _i32, _i32]),
+    "edv_masked_median": (C.c_int, [_fp, _fp, _i64, _f32, _f32, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_metrics_pred": (C.c_int, [_fp, _fp, _fp, _i64, _i32, _i32, _f64, _f64, _i32, _f32, _f32, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_metrics_errors": (C.c_int, [_fp, _fp, _i64, _i32, _i32, _f32, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_metrics_temporal": (C.c_int, [_fp, _fp, _i64, _i32, _i32, _f32, _fp, _fp, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_photometric_loss_workspace": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "edv_photometric_loss": (C.c_int, [_fp, C.POINTER(C.c_void_p), C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _f32, _f32, _f32,
                                        _fp, C.POINTER(C.c_void_p), _fp, C.c_size_t, C.c_void_p]),

@@ -263,6 +263,25 @@ int edv_stitch_apply(const float *disp_dev, int32_t ih, int32_t iw, const float 
     return stitch_apply(disp_dev, ih, iw, st_dev, tail_dev, new_dev, fh, fw, (hipStream_t)stream);
 }
 
+size_t edv_metrics_workspace(int64_t n, int32_t h, int32_t w) { return metrics_workspace(n, h, w); }
+int edv_masked_median(const float *x_dev, const float *gate_dev, int64_t count, float lo, float hi, double *out_dev, void *workspace_dev, size_t workspace_bytes,
+                      void *stream) {
+    return masked_median(x_dev, gate_dev, count, lo, hi, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+int edv_metrics_pred(const float *disp_dev, const float *gt_dev, float *pred_dev, int64_t n, int32_t h, int32_t w, double min_depth, double max_depth, int32_t align,
+                     float pred_depth_scale_factor, float eval_max_depth, double *scalars_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    return metrics_pred(disp_dev, gt_dev, pred_dev, n, h, w, min_depth, max_depth, align, pred_depth_scale_factor, eval_max_depth, scalars_dev, workspace_dev,
+                        workspace_bytes, (hipStream_t)stream);
+}
+int edv_metrics_errors(const float *pred_dev, const float *gt_dev, int64_t n, int32_t h, int32_t w, float eval_max_depth, double *out_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream) {
+    return metrics_errors(pred_dev, gt_dev, n, h, w, eval_max_depth, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+int edv_metrics_temporal(const float *pred_dev, const float *gt_dev, int64_t n, int32_t h, int32_t w, float eval_max_depth, const double *mats_dev, double *out_dev,
+                         float *warp_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    return metrics_temporal(pred_dev, gt_dev, n, h, w, eval_max_depth, mats_dev, out_dev, warp_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
 int edv_fold_lora(const float *W_dev, const float *A_dev, const float *B_dev, const float *U_dev, const float *V_dev, float scale, float *out_dev,
                   int32_t nout, int32_t nin, int32_t r, void *stream) {
     return fold_lora(W_dev, A_dev, B_dev, U_dev, V_dev, scale, out_dev, nout, nin, r, (hipStream_t)stream);

@@ -114,6 +114,14 @@ int resize_bicubic(const float *x, float *y, int NP, int H, int W, int OH, int O
 size_t stitch_workspace();  // bytes
 int stitch_fit(const float *disp, int ih, int iw, const float *tail, int fh, int fw, float *st, void *ws, size_t ws_bytes, hipStream_t stream);
 int stitch_apply(const float *disp, int ih, int iw, const float *st, float *tail, float *out_new, int fh, int fw, hipStream_t stream);
+// video-depth evaluation on the device (metrics.hip): a clip is [n, h, w]; scalars / results are doubles in device memory
+size_t metrics_workspace(long long n, int h, int w);  // bytes; n = h = w = 0: what masked_median, metrics_pred and metrics_errors need
+int masked_median(const float *x, const float *gate, long long count, float lo, float hi, double *out, void *ws, size_t ws_bytes, hipStream_t stream);
+int metrics_pred(const float *disp, const float *gt, float *pred, long long n, int h, int w, double min_depth, double max_depth, int align, float factor, float cap,
+                 double *scal, void *ws, size_t ws_bytes, hipStream_t stream);
+int metrics_errors(const float *pred, const float *gt, long long n, int h, int w, float cap, double *out, void *ws, size_t ws_bytes, hipStream_t stream);
+int metrics_temporal(const float *pred, const float *gt, long long n, int h, int w, float cap, const double *mats, double *out, float *warp, void *ws,
+                     size_t ws_bytes, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -811,7 +811,7 @@ class endodav(nn.Module):
         return int(_lib.load().edv_device_bytes(C.c_void_p(nat.handle))) if nat else 0
 
     # -------------------------------------------------------------------------------------
-    def infer_video_depth(self, frames, input_size=518, device="cuda", shard_windows=False, stitch="host"):
+    def infer_video_depth(self, frames, input_size=518, device="cuda", shard_windows=False, stitch="host", output="host"):
         """Sliding-window inference over a whole video (endodav.py:162-254).
 
         ``frames``: uint8 [N, H, W, 3].  Returns float32 [N, H, W].  Windows of 32 frames, step 22; the
@@ -821,7 +821,9 @@ class endodav(nn.Module):
         video and runs a share of its windows; rank 0 gets the result, the others None (``video.infer_video_depth``).
         ``stitch="device"`` (not in the reference, opt-in): the alignment and the cross-fade run on the GPU with fp64 sums instead of in numpy
         float32 on the host; the result agrees with the default's to about 1e-6 of its scale and is not bit-identical to it.
+        ``output="device"`` (needs ``stitch="device"``): the same result as a float32 ``torch.Tensor`` [N, H, W] on the GPU, never copied to the
+        host; all work is drained before the call returns (``video.infer_video_depth``).
         """
         from .video import infer_video_depth as _impl
 
-        return _impl(self, frames, input_size=input_size, device=device, shard_windows=shard_windows, stitch=stitch)
+        return _impl(self, frames, input_size=input_size, device=device, shard_windows=shard_windows, stitch=stitch, output=output)

@@ -1,7 +1,8 @@
 """Video-depth evaluation around ``infer_video_depth``: the counterpart of the reference's
 ``evaluate_depth_video.py:50-253``.
 
-Host-side numpy only — as in the reference — and shaped so that ``evaluate_video(model, dataset, ...)`` can be fed by
+Host-side numpy by default — as in the reference — or, opt-in, on the GPU (``metrics="device"``: ``clip_metrics_device`` over the kernels of
+``csrc/metrics.hip``); shaped so that ``evaluate_video(model, dataset, ...)`` can be fed by
 the reference's own ``SCAREDVideos`` loader (items are dicts with ``colors, depths, poses, Ks, filename``) or by
 ``SyntheticVideos`` below (the SCARED/Hamlyn frames are not in the build container).
 
@@ -103,18 +104,12 @@ def tas(depth_a, mask_a, i2w_a, depth_b, mask_b, i2w_b) -> float:
 
 
 # ---- harness ---------------------------------------------------------------------------------------------------------
-def _evaluate_clip(depther, item: dict, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device, stitch=None) -> Dict[str, object]:
-    """One clip of evaluate_depth_video.py:163-215: ``infer_video_depth`` -> depth -> alignment -> per-frame errors and
-    frame-to-frame TAE (x100) / TAS.  ``stitch`` reaches ``infer_video_depth`` only when it is given: a depther need not know it."""
+def clip_metrics_host(disp: np.ndarray, item: dict, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth) -> Dict[str, object]:
+    """Everything of evaluate_depth_video.py:163-215 after ``infer_video_depth``, in numpy on the host as in the reference: depth, alignment,
+    per-frame errors and frame-to-frame TAE (x100) / TAS of one clip.  -> ``{"errors", "temporal", "ratio", "align"}``."""
     MIN_DEPTH = 1e-3
-    colors, gts, poses, Ks = item["colors"], item["depths"], item["poses"], item["Ks"]
+    gts, poses, Ks = item["depths"], item["poses"], item["Ks"]
     rec: Dict[str, object] = {"errors": [], "temporal": [], "ratio": None, "align": None}
-    t0 = time.time()
-    kw = {} if device is None else {"device": device}
-    if stitch is not None:
-        kw["stitch"] = stitch
-    disp = depther.infer_video_depth(colors, **kw)
-    rec["time"] = time.time() - t0
     _, pred = disp_to_depth(disp, min_depth, max_depth)
     if depth_align == "scale":
         pred, ratio = median_scaling(gts, pred)
@@ -137,11 +132,96 @@ def _evaluate_clip(depther, item: dict, min_depth, max_depth, depth_align, pred_
     return rec
 
 
+ALIGN_MODES = {"scale": 1, "scale_shift": 2}  # edv_metrics_pred's ``align``; anything else: 0, no alignment
+
+
+def clip_metrics_device(disp_dev, item: dict, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, warp_out=None) -> Dict[str, object]:
+    """``clip_metrics_host`` on the GPU (``evaluate_video(metrics="device")``).  ``disp_dev``: the stitched disparity [n, h, w], a float32
+    ``torch.Tensor`` on the device (``infer_video_depth(stitch="device", output="device")``).  The clip's ground truth goes up once, the 4 x 4
+    matrices ``inv(K @ pose)`` and their inverses are made here in fp64 as on the host, and ``edv_metrics_pred`` / ``edv_metrics_errors`` /
+    ``edv_metrics_temporal`` run on the caller's current stream; the alignment scalars, the per-frame and the per-pair numbers come back in
+    ONE copy.  Same record as the host's: the same shapes, the same skipping of all-NaN rows, TAE x 100.
+
+    Against the host: the prediction is bit-identical for ``"scale"`` and no alignment, a1..a3, TAS and the ratio are equal; the means are
+    summed in fp64 here and in float32 on the host, so they agree to float32 rounding (tests/test_metrics_gpu.py).
+    ``warp_out`` (tests): a float32 device tensor [n-1, 2, h, w] that receives the resolved splats of every pair."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    lib = _lib.load()
+    if not (isinstance(disp_dev, torch.Tensor) and disp_dev.is_cuda and disp_dev.dtype == torch.float32 and disp_dev.dim() == 3):
+        raise ValueError("clip_metrics_device needs the stitched disparity as a float32 CUDA tensor [n, h, w] (infer_video_depth(stitch='device', output='device'))")
+    dev = disp_dev.device
+    n, h, w = disp_dev.shape
+    gts = np.ascontiguousarray(item["depths"], dtype=np.float32)
+    if gts.shape != (n, h, w):
+        raise ValueError(f"ground truth {gts.shape} does not match the prediction {(n, h, w)}")
+    mats = np.empty((n, 2, 4, 4), dtype=np.float64)
+    for i, (pose, K) in enumerate(zip(item["poses"], item["Ks"])):
+        mats[i, 0] = np.linalg.inv(K @ pose)
+        mats[i, 1] = np.linalg.inv(mats[i, 0])
+    rec: Dict[str, object] = {"errors": [], "temporal": [], "ratio": None, "align": None}
+    mode = ALIGN_MODES.get(depth_align, 0)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(_lib.stream_ptr(dev))
+        disp_dev = disp_dev.contiguous()
+        gt = torch.from_numpy(gts).to(dev)
+        mats_dev = torch.from_numpy(mats).to(dev)
+        pred = torch.empty_like(disp_dev)
+        res = torch.empty(8 + 8 * n + 2 * (n - 1), dtype=torch.float64, device=dev)  # scalars | per frame | per pair: one copy back
+        scal, err, tmp = res[:8], res[8:8 + 8 * n], res[8 + 8 * n:]
+        ws = torch.empty(int(lib.edv_metrics_workspace(n, h, w)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.edv_metrics_pred(disp_dev.data_ptr(), gt.data_ptr(), pred.data_ptr(), n, h, w, float(min_depth), float(max_depth), mode,
+                                        float(pred_depth_scale_factor), float(eval_max_depth), scal.data_ptr(), ws.data_ptr(), ws.numel(), st), "edv_metrics_pred")
+        _lib.check(lib.edv_metrics_errors(pred.data_ptr(), gt.data_ptr(), n, h, w, float(eval_max_depth), err.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                   "edv_metrics_errors")
+        if n > 1:
+            _lib.check(lib.edv_metrics_temporal(pred.data_ptr(), gt.data_ptr(), n, h, w, float(eval_max_depth), mats_dev.data_ptr(), tmp.data_ptr(),
+                                                _lib.ptr(warp_out), ws.data_ptr(), ws.numel(), st), "edv_metrics_temporal")
+        host = res.cpu().numpy()
+    if mode == 1 and not np.isnan(host[0]):
+        rec["ratio"] = float(host[0])
+    elif mode == 2:
+        rec["align"] = tuple(float(v) for v in host[1:5])
+    for row in host[8:8 + 8 * n].reshape(n, 8)[:, 1:]:
+        if not np.isnan(row).all():
+            rec["errors"].append(tuple(float(e) for e in row))
+    for t in host[8 + 8 * n:].reshape(n - 1, 2):
+        rec["temporal"].append([float(t[0]) * 100.0, float(t[1])])
+    return rec
+
+
+def _evaluate_clip(depther, item: dict, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device, stitch=None, metrics=None) -> Dict[str, object]:
+    """One clip of evaluate_depth_video.py:163-215: ``infer_video_depth`` -> depth -> alignment -> per-frame errors and
+    frame-to-frame TAE (x100) / TAS.  ``stitch`` reaches ``infer_video_depth`` only when it is given: a depther need not know it.
+    ``metrics="device"`` asks the depther for the stitched video on the GPU and computes everything after it there (``clip_metrics_device``)."""
+    on_device = metrics == "device"
+    t0 = time.time()
+    kw = {} if device is None else {"device": device}
+    if on_device:
+        kw["stitch"], kw["output"] = "device", "device"
+    elif stitch is not None:
+        kw["stitch"] = stitch
+    disp = depther.infer_video_depth(item["colors"], **kw)
+    elapsed = time.time() - t0
+    rec = (clip_metrics_device if on_device else clip_metrics_host)(disp, item, min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth)
+    rec["time"] = elapsed
+    return rec
+
+
 def evaluate_video(depther, dataset: Iterable[dict], *, min_depth: float = 0.1, max_depth: float = 150.0, depth_align: str = "scale",
                    pred_depth_scale_factor: float = 1.0, eval_max_depth: float = 150.0, device: str = "cuda",
-                   rank: Optional[int] = None, world: Optional[int] = None, stitch: Optional[str] = None) -> Optional[Dict[str, object]]:
+                   rank: Optional[int] = None, world: Optional[int] = None, stitch: Optional[str] = None,
+                   metrics: Optional[str] = None) -> Optional[Dict[str, object]]:
     """The loop of evaluate_depth_video.py:163-215.  ``depther`` only needs ``infer_video_depth(colors)``; ``stitch`` ("host" / "device",
     ``video.infer_video_depth``) is handed to it only when given.
+
+    ``metrics``: ``"host"`` (default) computes depth, alignment, errors and TAE / TAS in numpy as the reference does (``clip_metrics_host``);
+    ``"device"`` (opt-in) asks the depther for ``stitch="device", output="device"``, uploads the clip's ground truth once and computes all of
+    it on the GPU (``clip_metrics_device``), bringing back only the per-frame and per-pair numbers.  It does not combine with ``stitch="host"``.
 
     Clips are independent units: with ``world`` > 1 (default: the ``torch.distributed`` process group, if any) rank r
     evaluates clips r, r + world, ... on its own GPU -- indexed directly when the dataset supports ``len`` / ``[]`` (the reference's
@@ -149,9 +229,13 @@ def evaluate_video(depther, dataset: Iterable[dict], *, min_depth: float = 0.1, 
     the result equals the one-rank run's bit for bit.  The other ranks return None.  No collective on the data path."""
     from . import parallel
 
+    if metrics not in (None, "host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
+    if metrics == "device" and stitch not in (None, "device"):
+        raise ValueError("metrics='device' works on the video the device stitch leaves on the GPU: it does not combine with stitch='host'")
     if rank is None or world is None:
         rank, world = parallel.rank_world()
-    args = (min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device, stitch)
+    args = (min_depth, max_depth, depth_align, pred_depth_scale_factor, eval_max_depth, device, stitch, metrics)
     indexable = hasattr(dataset, "__getitem__") and hasattr(dataset, "__len__")
     if indexable:
         n_clips = len(dataset)

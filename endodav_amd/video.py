@@ -257,8 +257,10 @@ class HipWindowRunner:
             drain(k % nbuf)
         return results
 
-    def run_stitched(self, sources: Sequence[np.ndarray], n_keep: int) -> np.ndarray:
-        """``stitch="device"``: all windows of the video (``window_sources``) -> the stitched result [n_keep, fh, fw], float32, in pinned host memory.
+    def run_stitched(self, sources: Sequence[np.ndarray], n_keep: int, output: str = "host"):
+        """``stitch="device"``: all windows of the video (``window_sources``) -> the stitched result [n_keep, fh, fw], float32, in pinned host memory
+        (``output="host"``) or, by the same kernels and with the same bits, as a tensor on the device (``output="device"``: the final frames are
+        copied device-to-device instead of to the pinned buffer).  Either way all work is drained before the call returns.
 
         The windows run as in ``run``.  One more stream, the stitch stream, takes the lanes' ``ready`` events in window order and, for window k,
         fits (s, t) against the 8-frame tail of the output so far (edv_stitch_fit; k >= 1), writes the window's new frames and cross-fades the
@@ -272,8 +274,9 @@ class HipWindowRunner:
         dev, fh, fw = self.dev, self.fh, self.fw
         step = INFER_LEN - OVERLAP
         last = len(sources) - 1
+        on_device = output == "device"
         if last < 0:
-            return np.empty((0, fh, fw), dtype=np.float32)
+            return torch.empty((0, fh, fw), dtype=torch.float32, device=dev) if on_device else np.empty((0, fh, fw), dtype=np.float32)
         s_st = torch.cuda.Stream(device=dev)
         state: dict = {"done": 0}
 
@@ -282,7 +285,8 @@ class HipWindowRunner:
             state["ring"] = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32, device=dev) for _ in range(min(2, len(sources)))]
             state["st"] = torch.empty(2, dtype=torch.float32, device=dev)
             state["ws"] = torch.empty(int(lib.edv_stitch_workspace()), dtype=torch.uint8, device=dev)
-            state["out"] = torch.empty((n_keep, fh, fw), dtype=torch.float32, pin_memory=True)
+            # the device result comes from the caller's stream's pool and is first written on the stitch stream, which has waited for `entry`
+            state["out"] = torch.empty((n_keep, fh, fw), dtype=torch.float32, device=dev) if on_device else torch.empty((n_keep, fh, fw), dtype=torch.float32, pin_memory=True)
 
         def place(g: int) -> Tuple[int, int]:
             """(window, index in that window's buffer) of output frame g: window 0 holds frames 0..31, window k >= 1 frames 22 k + 10 .. 22 k + 31."""
@@ -319,7 +323,7 @@ class HipWindowRunner:
         self._run_windows(sources, begin, lambda k, slot: None, after_forward)
         s_st.synchronize()
         assert state["done"] == n_keep
-        return state["out"].numpy()
+        return state["out"] if on_device else state["out"].numpy()
 
     def resized_clip(self, source: np.ndarray) -> torch.Tensor:
         """The network input of one window, [1, 32, 3, th, tw] on the device (what ``run`` feeds the forward): for tests."""
@@ -335,7 +339,7 @@ class HipWindowRunner:
 
 
 # ---------------------------------------------------------------------------------------------
-def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None, shard_windows=False, rank=None, world=None, stitch="host"):
+def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None, shard_windows=False, rank=None, world=None, stitch="host", output="host"):
     """endodav.infer_video_depth (endodav.py:162-254).  By default every window of the video runs on the calling rank, whatever process group
     exists: that is what ``evaluate.evaluate_video`` needs, where each rank already holds a DIFFERENT clip (sharding the windows of those clips
     over the same ranks would pair up collectives of different clips -- ADVICE round 2).
@@ -351,12 +355,22 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
     the two agree to about 1e-6 of the output's scale on well-conditioned clips and are not bit-identical.  Its result lies in pinned host
     memory.  It does not combine with ``shard_windows=True``, which stitches on the host of rank 0.
 
+    ``output``: ``"host"`` (default) returns a numpy array; ``"device"`` (needs ``stitch="device"``, so it does not combine with
+    ``shard_windows=True`` either) returns the stitched video as a float32 ``torch.Tensor`` [n, fh, fw] on the GPU -- the same kernels and the
+    same bits, the final frames copied device-to-device instead of to the host (what ``evaluate.evaluate_video(metrics="device")`` consumes).
+    All work is drained before the call returns, as for the host result: the tensor can be used on any stream at once.
+
     ``runner``: anything with ``run(sources) -> [np.ndarray [32, H, W]]`` (default ``HipWindowRunner``; the gloo tests pass a stub);
-    ``stitch="device"`` needs its ``run_stitched(sources, n) -> np.ndarray [n, H, W]`` as well."""
+    ``stitch="device"`` needs its ``run_stitched(sources, n) -> np.ndarray [n, H, W]`` as well, and ``output="device"`` that it takes
+    ``output="device"``."""
     from . import parallel
 
     if stitch not in ("host", "device"):
         raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
+    if output not in ("host", "device"):
+        raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+    if output == "device" and (stitch != "device" or shard_windows):
+        raise ValueError("output='device' needs stitch='device' and does not combine with shard_windows=True: only the device stitch leaves the video on the GPU")
     if stitch == "device" and shard_windows:
         raise ValueError("stitch='device' does not combine with shard_windows=True: sharded windows are gathered and stitched on the host of rank 0")
     frames = np.asarray(frames)
@@ -370,7 +384,7 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
         runner = HipWindowRunner(model, np.ascontiguousarray(frames), dev)
     sources = window_sources(n)
     if stitch == "device":
-        return runner.run_stitched(sources, n)
+        return runner.run_stitched(sources, n, output="device") if output == "device" else runner.run_stitched(sources, n)
     if not shard_windows:
         return stitch_windows(runner.run(sources), n)
     if rank is None or world is None:

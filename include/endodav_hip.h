@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define EDV_ABI_VERSION 13 /* 13: test entry points for row-mapped GEMM / LayerNorm descriptors and the folds (edv_gemm_desc ... edv_bilinear_add); 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
+#define EDV_ABI_VERSION 14 /* 14: evaluation on the device (edv_metrics_workspace, edv_masked_median, edv_metrics_pred, edv_metrics_errors, edv_metrics_temporal); 13: test entry points for row-mapped GEMM / LayerNorm descriptors and the folds (edv_gemm_desc ... edv_bilinear_add); 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
 
 enum edv_lora_type { EDV_LORA_NONE = 0, EDV_LORA_LORA = 1, EDV_LORA_DVLORA = 2, EDV_LORA_SSB = 3, EDV_LORA_DASH = 4 };
 
@@ -269,6 +269,36 @@ int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *t
                    size_t workspace_bytes, void *stream);
 int edv_stitch_apply(const float *disp_dev, int32_t ih, int32_t iw, const float *st_dev, float *tail_dev, float *new_dev, int32_t fh, int32_t fw,
                      void *stream);
+
+/* ---- video-depth evaluation on the device (evaluate_video(metrics="device"); evaluate_depth_video.py:163-215, utils/utils.py:112-133,
+ * utils/layers.py:11-20, utils/eval_utils.py:63-143,265-282) ----
+ * A clip is [n, h, w] fp32; results and scalars are doubles in device memory (an fp32 value or a count is held exactly) and nothing comes back to
+ * the host.  Same input, same bits: sums are fp64 in a fixed order, the only atomics are integer ones.  No product is fused into a sum.
+ * edv_masked_median: out_dev[0] = np.median (float32 semantics: the middle order statistic, or the fp32 mean of the two middle ones) of x[i]
+ * over lo < gate[i] < hi, bit for bit; out_dev[1] = the number selected; none selected gives NaN.  Exact radix select (four 8-bit histogram
+ * passes, 64-bit counts).  x may alias gate.  Inputs are finite: NaN in x is unsupported, NaN in gate fails the comparison.
+ * edv_metrics_pred: pred = 1 / (1/max_depth + (1/min_depth - 1/max_depth) * disp); align 1 ("scale"): pred * (median gt / median pred);
+ * align 2 ("scale_shift"): (pred - t_pred) * (s_gt / s_pred) + t_gt with t the medians and s the mean absolute deviations (summed in fp64,
+ * rounded once to fp32), all over 1e-3 < gt < 150; then clip(pred * pred_depth_scale_factor, 1e-3, eval_max_depth).  fp32 operations in the
+ * order of the host's; align 0 and 1 are bit-identical to it.  scalars_dev [8]: ratio, t_gt, s_gt, t_pred, s_pred, selected count, 2 spare.
+ * edv_metrics_errors: out_dev [n][8] = valid count, abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 of each frame over 1e-3 < gt < eval_max_depth:
+ * fp32 terms as the host forms them, fp64 sums, divide and square root; a frame without a valid pixel gives NaN.
+ * edv_metrics_temporal: out_dev [n-1][2] = (tae, tas) of each consecutive pair (tae not yet x 100).  mats_dev [n][2][16]: per frame
+ * img2world = inv(K @ pose) and its inverse, row-major fp64, from the host.  fp64 geometry, every dot product a fixed left-to-right chain of
+ * explicit fused multiply-adds (the accumulation of the host's dgemm, so rounding ties fall as they fall there); the splat is a
+ * 64-bit atomic maximum of (source index + 1) << 32 | bits(float(z)), so the largest row-major source index wins a target pixel ("later
+ * points overwrite earlier ones"); one splat per direction serves tae and tas.  An empty overlap gives NaN.  warp_dev (may be NULL)
+ * [n-1][2][h][w] receives the resolved splats (a -> b, b -> a).  Pairs run in chunks of 4: the workspace does not grow with n.
+ * edv_metrics_workspace(n, h, w): bytes for every call above on such a clip, 16-byte aligned; (0, 0, 0): all but edv_metrics_temporal. */
+size_t edv_metrics_workspace(int64_t n, int32_t h, int32_t w);
+int edv_masked_median(const float *x_dev, const float *gate_dev, int64_t count, float lo, float hi, double *out_dev, void *workspace_dev, size_t workspace_bytes,
+                      void *stream);
+int edv_metrics_pred(const float *disp_dev, const float *gt_dev, float *pred_dev, int64_t n, int32_t h, int32_t w, double min_depth, double max_depth, int32_t align,
+                     float pred_depth_scale_factor, float eval_max_depth, double *scalars_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int edv_metrics_errors(const float *pred_dev, const float *gt_dev, int64_t n, int32_t h, int32_t w, float eval_max_depth, double *out_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+int edv_metrics_temporal(const float *pred_dev, const float *gt_dev, int64_t n, int32_t h, int32_t w, float eval_max_depth, const double *mats_dev, double *out_dev,
+                         float *warp_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* out = W + scale * (B∘V)(A∘U)  (U, V may be NULL): the LoRA / DV-LoRA fold of mylora/layers.py:148-157,384-393. */
 int edv_fold_lora(const float *W_dev, const float *A_dev, const float *B_dev, const float *U_dev, const float *V_dev, float scale, float *out_dev,
