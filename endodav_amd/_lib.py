@@ -11,7 +11,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EDV_LIB_PATH") or os.path.join(_HERE, "lib", "libendodav_hip.so")  # override: experiments only
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 LORA_TYPES = {"none": 0, "lora": 1, "dvlora": 2, "ssb": 3, "dash": 4}
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_SIGMOID_NEG = 0, 1, 2, 3, 4
@@ -156,6 +156,8 @@ SIGNATURES = {
     "edv_ssb_prep": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),
     "edv_sigmoid_bwd": (C.c_int, [_fp, _fp, _fp, _i64, C.c_void_p]),
     "edv_bilinear_add": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]),
+    # test entry point (ABI 15): the stream-K planners on a given slot count, no device
+    "edv_split_plan": (C.c_int, [_i32, _i64, _i32, _i32, C.POINTER(_i64)]),
 }
 
 

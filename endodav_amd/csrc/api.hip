@@ -1,5 +1,6 @@
 // extern "C" per-kernel entry points declared in include/endodav_hip.h (unit tests, micro-benchmarks).
 #include "../../include/endodav_hip.h"
+#include <algorithm>
 #include <vector>
 
 #include "ops.hpp"
@@ -359,6 +360,25 @@ int edv_bilinear_add(const float *x_dev, const float *add_dev, float *y_dev, int
                      void *stream) {
     EDV_CHECK(add_dev, "null addend");
     return bilinear(x_dev, y_dev, F, H, W, C, OH, OW, ACT_NONE, (hipStream_t)stream, add_dev);
+}
+
+// ---- test entry point (ABI 15): the launchers' planner and policies on a given slot count (tests/test_split_plan_cpu.py) ----
+int edv_split_plan(int32_t kind, int64_t tiles_or_tasks, int32_t slots, int32_t k_tiles, int64_t out[8]) {
+    EDV_CHECK(out && kind >= 0 && kind <= 3 && tiles_or_tasks > 0 && tiles_or_tasks < (1ll << 31) && k_tiles > 0, "kind 0..3, a positive count below 2^31");
+    if (kind == 3) {
+        const TaskSplit t = plan_tasks(tiles_or_tasks, k_tiles, slots, false);
+        const int64_t r[8] = {t.nsplit > 0, t.grid, t.whole_rounds, t.chunk, t.nsplit, t.leftover, t.units, (int64_t)t.pieces()};
+        std::copy(r, r + 8, out);
+        return 0;
+    }
+    const SplitPolicy &pol = kind == 0 ? gemm_dma_split_policy() : kind == 1 ? gemm_x6_split_policy() : conv_dma_split_policy();
+    GemmSplit sp{};
+    long long grid;
+    plan_plain(tiles_or_tasks, pol, &sp, &grid);
+    const bool split = plan_split(tiles_or_tasks, slots, k_tiles, pol, &sp, &grid);
+    const int64_t r[8] = {split, grid, sp.whole_rounds, sp.chunk, sp.nsplit, sp.stride, sp.units, split ? (int64_t)split_ws_floats(sp, pol) : 0};
+    std::copy(r, r + 8, out);
+    return 0;
 }
 
 size_t edv_trainer_loss_workspace(int32_t N, int32_t H, int32_t W) { return trainer_loss_workspace(N, H, W) * sizeof(float); }

@@ -876,74 +876,38 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float *__restri
     if (lse && ch == 0) lse[((long long)frame * heads + head) * N + qi] = M + log2f(lsum);
 }
 
-struct AttnPlan {
-    int nw, kt, grid, whole_rounds, chunk, ntasks, ntiles, leftover;
+struct AttnPlan : TaskSplit {  // the task split of streamk_plan.hpp, the kernel it is for and its workspace
+    int nw, kt, ntasks, ntiles;
     bool pipe, x6;
-    long long units;
     size_t ws_floats;
 };
 
 int pipe_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_lean_kernel, 256, 0) != hipSuccess) return 0;
-        if (getenv("EDV_DEBUG_SLOTS")) fprintf(stderr, "attn_lean_kernel: %d CUs x %d resident workgroups\n", cus, per_cu);
-        return cus * per_cu;
-    });
+    return resident_workgroups(cache, (const void *)attn_lean_kernel, 256, 0, 0, nullptr, "attn_lean_kernel");
 }
 bool use_pipe() {
-    static const bool on = [] {
-        const char *e = getenv("EDV_ATTN_LEAN");  // 0: the round-1 kernel (register-staged K/V, ~365 VALU instructions per key tile), for A/B runs
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = env_int("EDV_ATTN_LEAN", 1) != 0;  // 0: the round-1 kernel (register-staged K/V, ~365 VALU instructions per key tile), for A/B runs
     return on;
 }
 
 template <int NW, int KT>
 int resident_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_spatial_kernel<NW, KT>, NW * 64, 0) != hipSuccess) return 0;
-        return cus * per_cu;
-    });
+    return resident_workgroups(cache, (const void *)attn_spatial_kernel<NW, KT>, NW * 64, 0, 0, nullptr, nullptr);
 }
 
 int x6_attn_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipFuncSetAttribute((const void *)attn_x6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * X6_STAGE) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_x6_kernel, X6_NW * 64, 2 * X6_STAGE) != hipSuccess) return 0;
-        if (per_cu > 1) per_cu = 1;  // 96 KB of LDS
-        if (getenv("EDV_DEBUG_SLOTS")) fprintf(stderr, "attn_x6_kernel: %d CUs x %d resident workgroups\n", cus, per_cu);
-        return cus * per_cu;
-    });
+    return resident_workgroups(cache, (const void *)attn_x6_kernel, X6_NW * 64, 2 * X6_STAGE, 1 /* 96 KB of LDS */, nullptr, "attn_x6_kernel");
 }
 
 int make_plan(int F, int N, int heads, AttnPlan *p, bool x6 = false) {
     // 4 waves (128 queries) per workgroup share each staged K/V tile.  The 2- and 1-wave variants cost registers
     // (195 / 256 VGPRs) and measured slower on every shape tried (T=8: 79.9 vs 78.6 vs 68.5 TF/s); they are kept for
     // sequences shorter than one 128-query block and for experiments.
-    static const int forced = [] {
-        const char *e = getenv("EDV_ATTN_WAVES");
-        return e ? atoi(e) : 0;
-    }();
-    static const int kt_forced = [] {
-        const char *e = getenv("EDV_ATTN_KT");
-        return e ? atoi(e) : 0;
-    }();
-    static const int plain = [] {
-        const char *e = getenv("EDV_ATTN_PLAIN");  // 1: one workgroup per task (the pre-stream-K grid), for A/B runs
-        return e ? atoi(e) : 0;
-    }();
+    static const int forced = env_int("EDV_ATTN_WAVES", 0), kt_forced = env_int("EDV_ATTN_KT", 0);
+    static const int plain = env_int("EDV_ATTN_PLAIN", 0);  // 1: one workgroup per task (the pre-stream-K grid), for A/B runs
     int nw = N > 64 ? 4 : (N > 32 ? 2 : 1);
     if (forced == 1 || forced == 2 || forced == 4) nw = forced;
     p->nw = nw;
@@ -963,17 +927,8 @@ int make_plan(int F, int N, int heads, AttnPlan *p, bool x6 = false) {
     EDV_CHECK(!p->pipe || (long long)(N + 64) * heads * 3 * HD * 4 < (1ll << 31), "one frame's q|k|v rows exceed the 2 GB a buffer descriptor offset reaches");
     p->ntasks = (int)ntasks;
     p->ntiles = (N + p->kt - 1) / p->kt;
-    if (plain) {
-        p->grid = p->ntasks; p->whole_rounds = 1; p->leftover = 0; p->units = 0; p->chunk = 1; p->ws_floats = 0;
-        return 0;
-    }
-    p->whole_rounds = p->ntasks / slots;
-    p->leftover = p->ntasks - p->whole_rounds * slots;
-    p->units = (long long)p->leftover * p->ntiles;
-    p->chunk = p->units ? (int)((p->units + slots - 1) / slots) : 1;
-    p->grid = p->whole_rounds ? slots : (int)((p->units + p->chunk - 1) / p->chunk);
-    const int split_wgs = (int)((p->units + p->chunk - 1) / p->chunk);
-    p->ws_floats = (size_t)split_wgs * 2 * (size_t)(nw * 32) * (HD + 2);
+    static_cast<TaskSplit &>(*p) = plan_tasks(p->ntasks, p->ntiles, slots, plain != 0);
+    p->ws_floats = p->pieces() * (size_t)(nw * 32) * (HD + 2);
     return 0;
 }
 

@@ -304,48 +304,28 @@ __global__ __launch_bounds__(256) void attn_bwd_combine_kernel(const float *__re
         *reinterpret_cast<f32x4 *>(orow + 2 * D + (col - HD)) = acc;
 }
 
-struct BwdPlan {
-    int grid, whole_rounds, chunk, leftover, ntiles;
-    long long units;
-    size_t ws_floats;
-};
-
 template <int MODE, int NW>
 int bwd_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_spatial_bwd_kernel<MODE, NW>, NW * 64, 0) != hipSuccess) return 0;
-        return cus * per_cu;
-    });
+    return resident_workgroups(cache, (const void *)attn_spatial_bwd_kernel<MODE, NW>, NW * 64, 0, 0, nullptr, nullptr);
 }
 
+// one launch's task split (streamk_plan.hpp) and its workspace: two pieces of rb rows x oc columns per run
+struct BwdPlan : TaskSplit {
+    int ntiles;
+    size_t ws_floats;
+};
 BwdPlan make_bwd_plan(long long ntasks, int N, int slots, int rb, int oc, bool plain) {
-    BwdPlan p;
-    p.ntiles = (N + TR - 1) / TR;
-    if (plain || slots <= 0) {
-        p.grid = (int)ntasks; p.whole_rounds = 1; p.leftover = 0; p.units = 0; p.chunk = 1; p.ws_floats = 0;
-        return p;
-    }
-    p.whole_rounds = (int)(ntasks / slots);
-    p.leftover = (int)(ntasks - (long long)p.whole_rounds * slots);
-    p.units = (long long)p.leftover * p.ntiles;
-    p.chunk = p.units ? (int)((p.units + slots - 1) / slots) : 1;
-    p.grid = p.whole_rounds ? slots : (int)((p.units + p.chunk - 1) / p.chunk);
-    p.ws_floats = (size_t)((p.units + p.chunk - 1) / p.chunk) * 2 * (size_t)rb * oc;
-    return p;
+    const int ntiles = (N + TR - 1) / TR;
+    const TaskSplit t = plan_tasks(ntasks, ntiles, slots, plain);
+    return BwdPlan{t, ntiles, t.pieces() * (size_t)rb * oc};
 }
 
 }  // namespace
 
 namespace {
 bool bwd_plain() {
-    static const bool plain = [] {
-        const char *e = getenv("EDV_ATTN_BWD_PLAIN");  // 1: one workgroup per task (A/B runs)
-        return e && atoi(e) != 0;
-    }();
+    static const bool plain = env_int("EDV_ATTN_BWD_PLAIN", 0) != 0;  // 1: one workgroup per task (A/B runs)
     return plain;
 }
 }  // namespace

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 namespace edv {
@@ -80,6 +81,26 @@ struct DeviceSlotCache {
         return s;
     }
 };
+// Resident workgroups of a persistent kernel on the current device: CUs x workgroups per CU, cached in `cache`; 0 = a query failed.  Per CU it is
+// what the occupancy API answers for `threads` threads and `lds_bytes` of dynamic LDS (opted into first when not zero; `sibling`, an
+// instantiation launched with the same LDS size, gets the attribute too), at most `cap` (0: no cap -- the API over-reports where LDS bounds the
+// residency, and a persistent grid beyond what is really resident starts its surplus workgroups only when others finish), unless the environment
+// variable `override_env` gives a positive number.  EDV_DEBUG_SLOTS prints the result under `label` (null: silent).
+inline int resident_workgroups(DeviceSlotCache &cache, const void *kernel, int threads, size_t lds_bytes, int cap, const char *override_env, const char *label,
+                               const void *sibling = nullptr) {
+    return cache.get([&] {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        for (const void *k : {kernel, sibling})
+            if (k && lds_bytes && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes) != hipSuccess) return 0;
+        if (cap > 0 && per_cu > cap) per_cu = cap;
+        if (const char *e = override_env ? getenv(override_env) : nullptr) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
+        if (label && getenv("EDV_DEBUG_SLOTS")) fprintf(stderr, "%s: %d CUs x %d resident workgroups\n", label, cus, per_cu);
+        return cus * per_cu;
+    });
+}
 
 // Row remap: logical row m of a [frames * period] matrix lives at physical row
 //   (m / period) * stride + offset + inner * (m % period).
@@ -111,6 +132,12 @@ __device__ __forceinline__ float wave_max(float v) {
 // exact-erf GELU, the nn.GELU() / F.gelu default used everywhere in the reference
 // (layers/block.py:58, motion_module/attention.py:378)
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// an integer A/B knob from the environment (callers read it once: a function-local static)
+inline int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 

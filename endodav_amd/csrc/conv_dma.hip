@@ -26,7 +26,7 @@ namespace {
 constexpr int CBK = 32;
 __device__ __attribute__((aligned(256))) float g_zero_page[64];
 
-// SPLIT: the stream-K scheme of gemm_dma.hip for grids that do not fill the part (tiles <= resident workgroups, e.g. layer4_rn: 46
+// SPLIT: the stream-K scheme of streamk_plan.hpp / gemm_common.hpp for grids that do not fill the part (tiles <= resident workgroups, e.g. layer4_rn: 46
 // tiles of 108 k-tiles on 256 CUs): the tiles' k-tile units are cut into equal contiguous runs, one per workgroup; a run that does
 // not cover a tile's whole k range leaves its accumulators in a workspace slot and the last piece of a tile to arrive merges them in
 // run order and applies the epilogue.  SPLIT = false is the plain grid and compiles to the code it was before.
@@ -68,8 +68,7 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
             const long long left = u_end - u;
             kt1 = kt0 + left < nkt ? kt0 + (int)left : nkt;
             tile = lt;
-            // slot 0 = the piece that holds the run's first unit, slot 1 = the other one (the rule of gemm_dma.hip)
-            if (!(kt0 == 0 && kt1 == nkt)) part = sp.ws + ((long long)bid * 2 + (u == (long long)bid * sp.chunk ? 0 : 1)) * SPLIT_SLOT;
+            if (!(kt0 == 0 && kt1 == nkt)) part = split_slot<SPLIT_SLOT>(sp, bid, u);  // a piece: not the tile's whole k range
             u += kt1 - kt0;
         } else {
             if (!once) break;
@@ -222,33 +221,20 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
             if (kt < kt1) ktile(kt, std::integral_constant<int, 0>{});
         }
         if (SPLIT && part) {
-            // the piece exchange of gemm_dma.hip: agent-scope relaxed atomics (sc1 write-through stores / L2-bypassing loads), an
-            // arrival counter per tile, the last piece to arrive sums all pieces in run order
+            // piece hand-off (gemm_common.hpp); both LDS stages are idle here
 #pragma unroll
             for (int r = 0; r < 16; ++r) __hip_atomic_store(&part[(wave * 16 + r) * 64 + lane], acc[0][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const long long ub = (long long)lt * nkt;
-            const int g0 = (int)(ub / sp.chunk), g1 = (int)((ub + nkt - 1) / sp.chunk);
-            int *s_last = reinterpret_cast<int *>(smem);  // both LDS stages are idle here
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                const int arrived = __hip_atomic_fetch_add(&sp.cnt[lt], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int last = arrived == g1 - g0;
-                if (last) __hip_atomic_store(&sp.cnt[lt], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (last) split_merge_acquire();  // this CU's L1 may hold stale lines of the piece slots (gemm_common.hpp)
-                *s_last = last;
-            }
-            __syncthreads();
-            const bool last = *s_last != 0;
-            __syncthreads();
+            int g0, g1;
+            const bool last = split_handoff(sp, &sp.cnt[lt], ub, nkt, reinterpret_cast<int *>(smem), tid, g0, g1);
             if (last) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
                 const float *base = sp.ws + (wave * 16) * 64 + lane;
                 int gg = g0;
                 for (; gg + 1 <= g1; gg += 2) {
-                    const float *qa = base + ((long long)gg * 2 + ((long long)gg * sp.chunk >= ub ? 0 : 1)) * SPLIT_SLOT;
-                    const float *qb = base + ((long long)(gg + 1) * 2 + ((long long)(gg + 1) * sp.chunk >= ub ? 0 : 1)) * SPLIT_SLOT;
+                    const float *qa = split_piece<SPLIT_SLOT>(base, sp, gg, ub);
+                    const float *qb = split_piece<SPLIT_SLOT>(base, sp, gg + 1, ub);
                     float ta[16], tb[16];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
@@ -259,7 +245,7 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
                     for (int r = 0; r < 16; ++r) acc[0][0][r] = (acc[0][0][r] + ta[r]) + tb[r];
                 }
                 if (gg <= g1) {
-                    const float *qa = base + ((long long)gg * 2 + ((long long)gg * sp.chunk >= ub ? 0 : 1)) * SPLIT_SLOT;
+                    const float *qa = split_piece<SPLIT_SLOT>(base, sp, gg, ub);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[0][0][r] += __hip_atomic_load(qa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -282,61 +268,36 @@ void launch_variant(const GemmDesc &d, const GemmSplit &sp, bool buf, unsigned g
 // the kernel specialization silently invalid -- "no matching function" at the launch, or an undefined __device_stub__ at load time -- while
 // the device pass compiles it.  Hence the explicit (unsigned) / (int) casts on the buffer-load offsets.)
 template <int WGM, int EP>
-int conv_slots_query() {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    void (*kern)(const GemmDesc, const GemmSplit) = conv3_dma_kernel<WGM, EP, true, true>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess) return 0;
-    if (per_cu > 4) per_cu = 4;  // 32 KB of LDS: the API says 5, the part places 4 (scratch/ubench/lds_residency.hip)
-    return cus * per_cu;
-}
-template <int WGM, int EP>
 int conv_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] { return conv_slots_query<WGM, EP>(); });
+    // at most 4: 32 KB of LDS -- the API says 5, the part places 4 (scratch/ubench/lds_residency.hip)
+    return resident_workgroups(cache, (const void *)conv3_dma_kernel<WGM, EP, true, true>, 256, 0, 4, nullptr, nullptr);
 }
 
 template <int WGM, int EP>
 int launch_conv_ep(const GemmDesc &d, long long tiles, hipStream_t st) {
-    static const bool split_on = [] {
-        const char *e = getenv("EDV_CONV_SPLIT");  // 0: plain grid always (A/B runs)
-        return !(e && atoi(e) == 0);
-    }();
-    static const bool buf_off = [] {
-        const char *e = getenv("EDV_CONV_BUF");  // 0: flat 64-bit DMA source addresses + zero page as in round 1 (A/B runs)
-        return e && atoi(e) == 0;
-    }();
+    static const bool split_on = env_int("EDV_CONV_SPLIT", 1) != 0;  // 0: plain grid always (A/B runs)
+    static const bool buf_off = env_int("EDV_CONV_BUF", 1) == 0;     // 0: flat 64-bit DMA source addresses + zero page as in round 1 (A/B runs)
     // 32-bit byte offsets must reach every tap of every pixel, with room for the "beyond the end" offset of padding lanes
     const long long frames = (d.M - 1) / ((long long)d.cOH * d.cOW) + 1;
     // ... and (the buffer epilogue) every element of C, R1 and R2
     const long long ld_out = std::max(std::max(d.ldc, d.R1 ? d.ldr1 : 0), d.R2 ? d.ldr2 : 0);
     const bool buf = !buf_off && frames * d.cH * d.cW * d.cC * 4 < (1ll << 31) - (1 << 20) && (long long)d.N * d.ldw * 4 < (1ll << 32) - (1 << 20) &&
                      (d.M + 64) * ld_out * 4 < (1ll << 32) - 4096;  // rows up to 63 past M must not wrap the 32-bit scalar offsets (gemm_dma.hip, fits_buffer)
-    const int nkt = d.K / CBK;
-    GemmSplit sp{0, 1, 0, 1, 0, nullptr, nullptr};
-    const int slots = conv_slots<WGM, EP>();
-    // grids that do not fill the part and whose tiles are deep (Cin >= 192: 54+ k-tiles), or that leave most of it idle (8 tiles per
-    // resident slot).  Measured (scratch/kb_conv_split.py, plain / split us): layer4_rn 46 tiles x 108 k-tiles 91 / 31, resize_layers.3
-    // 276 x 108: 144 / 89, layer3_rn 172 x 54: 48 / 38, RCU at 19x19 46 x 18: 18.9 / 14.2 -- but RCU at 37x37 172 x 18: 19.3 / 24.9 and at
-    // 74x74 685 x 18: 39.8 / 46.4, so shallow tiles on a half-full grid stay plain.
-    if (split_on && d.ws && slots > 0 && tiles > 16 && tiles <= slots && tiles <= SPLIT_MAX_COUNTERS && nkt >= 18 &&
-        (nkt >= 48 || tiles * 8 <= slots)) {
-        sp.units = tiles * nkt;
-        long long chunk = (sp.units + slots - 1) / slots;
-        const long long chunk_min = (nkt + 3) / 4;
-        chunk = chunk > chunk_min ? chunk : chunk_min;
-        sp.chunk = (int)chunk;
-        sp.nsplit = (int)((sp.units + chunk - 1) / chunk);
-        sp.cnt = reinterpret_cast<int *>(d.ws);
-        sp.ws = d.ws + SPLIT_MAX_COUNTERS;
-        if ((size_t)SPLIT_MAX_COUNTERS + (size_t)sp.nsplit * 2 * SPLIT_SLOT <= d.ws_floats && (uintptr_t)d.ws % 16 == 0) {
-            launch_variant<WGM, EP, true>(d, sp, buf, (unsigned)sp.nsplit, st);
+    const SplitPolicy &pol = conv_dma_split_policy();
+    GemmSplit sp{};
+    long long grid;
+    plan_plain(tiles, pol, &sp, &grid);
+    if (split_on && d.ws && plan_split(tiles, conv_slots<WGM, EP>(), d.K / CBK, pol, &sp, &grid)) {
+        split_bind(&sp, d.ws, pol);
+        if (split_ws_floats(sp, pol) <= d.ws_floats && (uintptr_t)d.ws % 16 == 0) {
+            launch_variant<WGM, EP, true>(d, sp, buf, (unsigned)grid, st);
             EDV_LAUNCH_OK();
             return 0;
         }
+        grid = tiles;  // a workspace too small for this plan: the plain grid (which does not read sp)
     }
-    launch_variant<WGM, EP, false>(d, sp, buf, (unsigned)tiles, st);
+    launch_variant<WGM, EP, false>(d, sp, buf, (unsigned)grid, st);
     EDV_LAUNCH_OK();
     return 0;
 }
@@ -354,6 +315,16 @@ int launch_conv(const GemmDesc &d, hipStream_t st) {
 }
 
 }  // namespace
+
+// Which launches split: grids that do not fill the part and whose tiles are deep (Cin >= 192: 54+ k-tiles), or that leave most of it idle (8 tiles
+// per resident slot).  Measured (scratch/kb_conv_split.py, plain / split us): layer4_rn 46 tiles x 108 k-tiles 91 / 31, resize_layers.3
+// 276 x 108: 144 / 89, layer3_rn 172 x 54: 48 / 38, RCU at 19x19 46 x 18: 18.9 / 14.2 -- but RCU at 37x37 172 x 18: 19.3 / 24.9 and at
+// 74x74 685 x 18: 39.8 / 46.4, so shallow tiles on a half-full grid stay plain.
+const SplitPolicy &conv_dma_split_policy() {
+    static const SplitPolicy p{.min_kt = 18, .min_tiles = 16, .max_rounds = 0, .widen = false, .counters = SPLIT_MAX_COUNTERS, .slot_floats = SPLIT_SLOT,
+                               .whole_rounds = false, .deep_kt = 48, .idle_factor = 8};
+    return p;
+}
 
 bool conv_dma_supported(const GemmDesc &d) {
     return d.loader == LOAD_CONV3 && d.store == STORE_ROWS && d.cC % CBK == 0 && d.K == 9 * d.cC && d.ldw % 4 == 0 && d.M > 0 && d.N > 0;

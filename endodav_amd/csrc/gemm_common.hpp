@@ -14,14 +14,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     return v;
 }
 
-// Stream-K work split of one launch of the LDS-DMA kernels (gemm_dma.hip explains the scheme; conv_dma.hip uses it for small grids).
-struct GemmSplit {
-    int whole_rounds, chunk, nsplit, stride;
-    long long units;
-    float *ws;   // piece slots (after the counters)
-    int *cnt;    // one arrival counter per split tile
-    int group_m = 1;  // gemm_x6.hip: row blocks per tile group of its tile order
-};
 // The merging workgroup's acquire (round 3).  The piece exchange stores and loads every piece word sc1 behind a drained, barrier-ordered counter add:
 // the form MI355X_MICROARCH.md ("Valid forms") measures as sufficient WITHOUT an acquire -- but only at one workgroup per CU, and the split launches
 // run three.  Outside that table the guide says "keep the acquire", so the ONE lane whose counter add completes a tile invalidates its CU's L1
@@ -39,7 +31,78 @@ __device__ __forceinline__ void split_merge_acquire() {
 }
 constexpr int SPLIT_SLOT = 64 * 64;        // floats per piece: a 64x64 or 128x32 tile in accumulator order, (wave * 16 + r) * 64 + lane
 constexpr int SPLIT_MAX_COUNTERS = 4096;   // >= the tiles a launch may split
+// EDV_GEMM_PLAIN=1: one workgroup per tile even with a workspace (A/B runs of gemm_dma.hip and gemm_x6.hip)
+inline bool gemm_plain_forced() {
+    static const bool on = env_int("EDV_GEMM_PLAIN", 0) != 0;
+    return on;
+}
 
+// ---- device side of the stream-K split (streamk_plan.hpp has the scheme and the host planner) ------------------------------------------------
+// Used by gemm_dma.hip, conv_dma.hip and gemm_x6.hip.  Their form is what kept every kernel's instruction stream unchanged when they were factored
+// out: GemmSplit travels BY VALUE (through a reference the kernel-argument loads lose their amdgpu.noclobber marking and the merge's addressing
+// changes), and the segment arithmetic, the piece stores and the merge loops stay in each kernel (moving them moved the generated code).
+// Run cursor: the run a workgroup owns (run j = bid / stride; only workgroups with bid % stride == 0 and j < nsplit own one; -1: none), its first
+// unit, one past its last.
+__device__ __forceinline__ int split_run(const GemmSplit sp, bool split, int bid) {
+    return (split && sp.units > 0 && bid % sp.stride == 0 && bid / sp.stride < sp.nsplit) ? bid / sp.stride : -1;
+}
+__device__ __forceinline__ long long split_run_begin(const GemmSplit sp, int run) { return run >= 0 ? (long long)run * sp.chunk : 0; }
+__device__ __forceinline__ long long split_run_end(const GemmSplit sp, int run, long long u) {
+    return run >= 0 ? (u + sp.chunk < sp.units ? u + sp.chunk : sp.units) : 0;
+}
+// The slot rule.  A run longer than a tile's k range has up to three segments: the tail of a tile, whole tiles, the head of a tile.  Only the first
+// and the last can be pieces.  Slot 0 = the piece that holds the run's first unit, slot 1 = the other one.  split_slot is the producer's side (the
+// segment of run `run` that starts at unit u; SLOT floats per piece), split_piece the merge's, from the tile's side: run start inside the tile -> slot 0.
+template <int SLOT>
+__device__ __forceinline__ float *split_slot(const GemmSplit sp, int run, long long u) {
+    return sp.ws + ((long long)run * 2 + (u == (long long)run * sp.chunk ? 0 : 1)) * SLOT;
+}
+// run g's piece of the split tile whose first unit is ub, relative to `base` (sp.ws plus, or followed by, the lane's offset inside a piece)
+template <int SLOT>
+__device__ __forceinline__ const float *split_piece(const float *base, const GemmSplit sp, int g, long long ub) {
+    return base + ((long long)g * 2 + ((long long)g * sp.chunk >= ub ? 0 : 1)) * SLOT;
+}
+
+// Piece hand-off.  Pieces travel between workgroups on different XCDs (separate L2s, non-coherent L1s).  An agent-scope
+// release / acquire fence pair would do it, but on this part the release writes back the WHOLE L2 (buffer_wbl2) -- measured
+// +140 us per launch with every other workgroup's output tiles dirty in it.  Instead:
+//   producer  every piece word is stored with an agent-scope relaxed atomic store (global_store ... sc1: write-through);
+//             every storing wave then executes s_waitcnt vmcnt(0) (its stores are acknowledged), the workgroup meets at a
+//             barrier, and ONE lane adds 1 to the tile's agent-scope counter;
+//   consumer  the workgroup whose add returns "all pieces in" broadcasts that through LDS behind a workgroup barrier and
+//             reads every piece word with agent-scope relaxed atomic loads (global_load ... sc1: served by L2, never by this
+//             CU's L1), in run order whatever the arrival order was.
+// This is the "sc1 stores + drained counter + sc1 loads" hand-off the CDNA4 guide measures as valid (MI355X_MICROARCH.md,
+// Workgroup dispatch ..., Valid forms: one lane signals for all of its workgroup's stores after every wave's vmcnt(0) and
+// the barrier; every load of the handed-off bytes is an sc1 load issued after the add has returned and a barrier) -- measured
+// there at ONE workgroup per CU; these launches run up to four, so the merging workgroup also executes the agent-scope acquire the
+// guide prescribes outside its table (split_merge_acquire above).  It is
+// an ISA-level contract of gfx950 / ROCm 7.2, NOT a guarantee of the C++ memory model: the __syncthreads() between the
+// counter add and the loads is what keeps the compiler from hoisting the loads (a workgroup-scope fence), the hardware
+// ordering comes from sc1.  tests/test_streamk_fuzz_gpu.py::test_piece_exchange_contract_under_uneven_load is the gate to
+// re-run after a toolchain change; the fenced form to switch to is spelled out there.
+//
+// split_handoff: what follows a workgroup's piece stores for split tile lt (the stores themselves stay with each kernel: they differ in the
+// accumulators a wave holds).  cnt = &sp.cnt[lt], ub = lt * nkt = the tile's first unit.  Returns, to every thread of the workgroup, whether this
+// was the tile's last piece to arrive -- the workgroup then merges runs g0 .. g1 (the runs whose unit ranges intersect [ub, ub + nkt)) with
+// agent-scope loads in run order (split_piece) and applies the epilogue.  s_last: one int of LDS that is idle between the k loop and the next
+// tile's first staging write.
+__device__ __forceinline__ bool split_handoff(const GemmSplit sp, int *cnt, long long ub, int nkt, int *s_last, int tid, int &g0, int &g1) {
+    g0 = (int)(ub / sp.chunk), g1 = (int)((ub + nkt - 1) / sp.chunk);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const int arrived = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = arrived == g1 - g0;
+        if (last) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all pieces in: zero for the next launch
+        if (last) split_merge_acquire();  // this CU's L1 may hold stale lines of the piece slots
+        *s_last = last;
+    }
+    __syncthreads();
+    const bool last = *s_last != 0;
+    __syncthreads();  // s_last is read before the next tile's staging may overwrite it
+    return last;
+}
 
 // XCD-aware, bijective block remap: blocks b and b+8 share an XCD (and its L2); give each XCD a contiguous run of
 // logical tiles so that tiles sharing an operand panel hit the same L2.

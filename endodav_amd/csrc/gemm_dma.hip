@@ -34,20 +34,12 @@ namespace {
 constexpr int DBK = 32, DBM = 64, DBN = 64;
 constexpr int DSTAGE = (DBM + DBN) * DBK;  // floats per stage (16 KB)
 
-// Work split of one launch (host-made, passed by value).  G = gridDim.x persistent workgroups, all co-resident (3 per CU: the split
-// instantiation holds ~116 VGPRs, and a grid beyond the real residency loses everything the split gains).  Every workgroup first computes `whole_rounds` whole output tiles
-// (tile = round * G + id).  The remaining tiles % G tiles are `units` = leftover_tiles * k_tiles k-tile units; they are cut into
-// `nsplit` contiguous runs of `chunk` units, run j going to the workgroup with id j * stride (spread over the CUs).  A run that
-// does not cover a tile's whole k range leaves its raw accumulators in workspace slot (j * 2 + segment), bumps the tile's
-// arrival counter, and the LAST run to arrive sums all pieces of that tile in run order (so the result does not depend on the
-// arrival order) and applies the epilogue: no fix-up launch, no spinning.  The counters live at the head of the workspace, must
-// be zero before the first launch, and are left zero by every launch.  Without a workspace the launch is the plain grid:
-// G = tiles, one whole tile each.
+// Work split: the persistent grid with a stream-K tail of streamk_plan.hpp (scheme and host planner; the device side is in gemm_common.hpp).
+// Here 3 workgroups per CU: the split instantiation holds ~116 VGPRs, and a grid beyond the real residency loses everything the split gains.
 //
 // Why it matters (profiles/r01_gemm_tile_sweep.txt, warm clocks): a CU retires tiles at a fixed MFMA-bound rate, so a grid of
 // 1032 tiles on 256 CUs (N = 384 at 8 x 1370 rows) takes as long as 1280 tiles: fc2 138 us vs 112 us at 1020 tiles; with the split
 // 121 us.  It pays for deep tiles (K >= 768) and for small grids; 12-k-tile tiles lose more to the static assignment than they gain.
-// (GemmSplit, SLOT and MAX_COUNTERS live in gemm_common.hpp: conv_dma.hip uses the same scheme)
 constexpr int SLOT = SPLIT_SLOT;
 constexpr int MAX_COUNTERS = SPLIT_MAX_COUNTERS;
 
@@ -84,10 +76,9 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
     const int swa = (ra >> 1) & 7, swb = (rb >> 1) & 7;
 
     const int tile_l0 = sp.whole_rounds * G;
-    // run j = bid / stride of the split (only workgroups with bid % stride == 0 and j < nsplit own one)
-    const int run = (SPLIT && sp.units > 0 && bid % sp.stride == 0 && bid / sp.stride < sp.nsplit) ? bid / sp.stride : -1;
-    long long u = run >= 0 ? (long long)run * sp.chunk : 0;
-    const long long u_end = run >= 0 ? (u + sp.chunk < sp.units ? u + sp.chunk : sp.units) : 0;
+    const int run = split_run(sp, SPLIT, bid);
+    long long u = split_run_begin(sp, run);
+    const long long u_end = split_run_end(sp, run, u);
     int round = 0;
     for (;;) {
         int tile, kt0, kt1, lt = 0;
@@ -104,10 +95,7 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
             kt1 = kt0 + left < nkt ? kt0 + (int)left : nkt;
             tile = tile_l0 + t;
             lt = t;
-            // A run longer than a tile's k range has up to three segments: the tail of a tile, whole tiles, the head of a tile.  Only
-            // the first and the last can be pieces.  Slot 0 = the piece that holds the run's first unit, slot 1 = the other one -- the
-            // rule the merge applies from the tile's side (run start inside the tile -> slot 0).
-            if (!(kt0 == 0 && kt1 == nkt)) part = sp.ws + ((long long)run * 2 + (u == (long long)run * sp.chunk ? 0 : 1)) * SLOT;
+            if (!(kt0 == 0 && kt1 == nkt)) part = split_slot<SLOT>(sp, run, u);  // a piece: not the tile's whole k range
             u += kt1 - kt0;
         } else {
             break;
@@ -231,50 +219,21 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
         }
         EDV_GEMM_STAMP(3);
         if (SPLIT && part) {
-            // Piece hand-off.  Pieces travel between workgroups on different XCDs (separate L2s, non-coherent L1s).  An agent-scope
-            // release / acquire fence pair would do it, but on this part the release writes back the WHOLE L2 (buffer_wbl2) -- measured
-            // +140 us per launch with every other workgroup's output tiles dirty in it.  Instead:
-            //   producer  every piece word is stored with an agent-scope relaxed atomic store (global_store ... sc1: write-through);
-            //             every storing wave then executes s_waitcnt vmcnt(0) (its stores are acknowledged), the workgroup meets at a
-            //             barrier, and ONE lane adds 1 to the tile's agent-scope counter;
-            //   consumer  the workgroup whose add returns "all pieces in" broadcasts that through LDS behind a workgroup barrier and
-            //             reads every piece word with agent-scope relaxed atomic loads (global_load ... sc1: served by L2, never by this
-            //             CU's L1), in run order whatever the arrival order was.
-            // This is the "sc1 stores + drained counter + sc1 loads" hand-off the CDNA4 guide measures as valid (MI355X_MICROARCH.md,
-            // Workgroup dispatch ..., Valid forms: one lane signals for all of its workgroup's stores after every wave's vmcnt(0) and
-            // the barrier; every load of the handed-off bytes is an sc1 load issued after the add has returned and a barrier) -- measured
-            // there at ONE workgroup per CU; this launch runs three, so the merging workgroup also executes the agent-scope acquire the
-            // guide prescribes outside its table (split_merge_acquire, gemm_common.hpp).  It is
-            // an ISA-level contract of gfx950 / ROCm 7.2, NOT a guarantee of the C++ memory model: the __syncthreads() between the
-            // counter add and the loads is what keeps the compiler from hoisting the loads (a workgroup-scope fence), the hardware
-            // ordering comes from sc1.  tests/test_streamk_fuzz_gpu.py::test_piece_exchange_contract_under_uneven_load is the gate to
-            // re-run after a toolchain change; the fenced form to switch to is spelled out there.
+            // piece hand-off (gemm_common.hpp: sc1 stores, every wave's vmcnt(0), barrier, one agent-scope counter add; the last arriver acquires
+            // and then reads every piece with sc1 loads in run order); both LDS stages are idle between the k loop and the next tile's first DMA
 #pragma unroll
             for (int r = 0; r < 16; ++r) __hip_atomic_store(&part[(wave * 16 + r) * 64 + lane], acc[0][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // pieces of leftover tile lt: the runs whose unit ranges intersect [lt * nkt, (lt + 1) * nkt)
             const long long ub = (long long)lt * nkt;
-            const int g0 = (int)(ub / sp.chunk), g1 = (int)((ub + nkt - 1) / sp.chunk);
-            int *s_last = reinterpret_cast<int *>(smem);  // both LDS stages are idle between the k loop and the next tile's first DMA
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                const int arrived = __hip_atomic_fetch_add(&sp.cnt[lt], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int last = arrived == g1 - g0;
-                if (last) __hip_atomic_store(&sp.cnt[lt], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all pieces in: zero for the next launch
-                if (last) split_merge_acquire();  // this CU's L1 may hold stale lines of the piece slots (gemm_common.hpp)
-                *s_last = last;
-            }
-            __syncthreads();
-            const bool last = *s_last != 0;
-            __syncthreads();  // s_last is read before the next tile's DMA may overwrite it
+            int g0, g1;
+            const bool last = split_handoff(sp, &sp.cnt[lt], ub, nkt, reinterpret_cast<int *>(smem), tid, g0, g1);
             if (last) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
                 const float *base = sp.ws + (wave * 16) * 64 + lane;
                 int gg = g0;
                 for (; gg + 1 <= g1; gg += 2) {  // two pieces in flight; summed in run order whatever the arrival order was
-                    const float *pa = base + ((long long)gg * 2 + ((long long)gg * sp.chunk >= ub ? 0 : 1)) * SLOT;
-                    const float *pb = base + ((long long)(gg + 1) * 2 + ((long long)(gg + 1) * sp.chunk >= ub ? 0 : 1)) * SLOT;
+                    const float *pa = split_piece<SLOT>(base, sp, gg, ub);
+                    const float *pb = split_piece<SLOT>(base, sp, gg + 1, ub);
                     float ta[16], tb[16];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
@@ -285,7 +244,7 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
                     for (int r = 0; r < 16; ++r) acc[0][0][r] = (acc[0][0][r] + ta[r]) + tb[r];
                 }
                 if (gg <= g1) {
-                    const float *pa = base + ((long long)gg * 2 + ((long long)gg * sp.chunk >= ub ? 0 : 1)) * SLOT;
+                    const float *pa = split_piece<SLOT>(base, sp, gg, ub);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[0][0][r] += __hip_atomic_load(pa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -315,110 +274,72 @@ inline bool fits_buffer(const GemmDesc &d) {
 template <int STORE, int EP>
 int dma_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_dma_kernel<STORE, EP, true, 2>, 256, 0) != hipSuccess) return 0;
-        // The occupancy API answers 5 (5 x 32 KB = the whole 160 KB of LDS), the hardware places 4: the timeline of
-        // scratch/ubench/gemm_trace.hip shows exactly 4 x 256 workgroups alive.  A persistent grid must match what is really
-        // resident, or the surplus workgroups start only when others finish.  EDV_GEMM_SLOTS_PER_CU overrides.
-        if (per_cu > 4) per_cu = 4;
-        // ... and 3 is what the split runs with: at 3 and at 4 persistent workgroups per CU the step takes the same time (interleaved A/B,
-        // profiles/r02_notes.txt), and 768 runs leave a quarter fewer pieces to write and re-read than 1024 (fc2 at T = 8: 32 vs 48 MB written).
-        if (per_cu > 3) per_cu = 3;
-        if (const char *e = getenv("EDV_GEMM_SLOTS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
-        if (getenv("EDV_DEBUG_SLOTS")) fprintf(stderr, "gemm_dma_kernel<%d,%d>: %d CUs x %d resident workgroups\n", STORE, EP, cus, per_cu);
-        return cus * per_cu;
-    });
+    static const std::string label = "gemm_dma_kernel<" + std::to_string(STORE) + "," + std::to_string(EP) + ">";
+    // The occupancy API answers 5 (5 x 32 KB = the whole 160 KB of LDS), the hardware places 4: the timeline of
+    // scratch/ubench/gemm_trace.hip shows exactly 4 x 256 workgroups alive.  A persistent grid must match what is really
+    // resident, or the surplus workgroups start only when others finish.  EDV_GEMM_SLOTS_PER_CU overrides.
+    constexpr int placed = 4;
+    // ... and 3 is what the split runs with: at 3 and at 4 persistent workgroups per CU the step takes the same time (interleaved A/B,
+    // profiles/r02_notes.txt), and 768 runs leave a quarter fewer pieces to write and re-read than 1024 (fc2 at T = 8: 32 vs 48 MB written).
+    constexpr int cap = placed > 3 ? 3 : placed;
+    return resident_workgroups(cache, (const void *)gemm_dma_kernel<STORE, EP, true, 2>, 256, 0, cap, "EDV_GEMM_SLOTS_PER_CU", label.c_str());
+}
+
+template <int STORE, int EP, bool SPLIT>
+void launch_variant(const GemmDesc &d, const GemmSplit &sp, bool buf, long long grid, hipStream_t st) {
+    if (buf && d.a_map.period == 0) EDV_LAUNCH((gemm_dma_kernel<STORE, EP, SPLIT, 2>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
+    else if (buf) EDV_LAUNCH((gemm_dma_kernel<STORE, EP, SPLIT, 1>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
+    else EDV_LAUNCH((gemm_dma_kernel<STORE, EP, SPLIT, 0>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
 }
 
 template <int STORE, int EP>
 int launch_dma(const GemmDesc &d, long long tiles, hipStream_t st) {
-    static const bool plain_forced = [] {
-        const char *e = getenv("EDV_GEMM_PLAIN");  // 1: one workgroup per tile even with a workspace (A/B runs)
-        return e && atoi(e) != 0;
-    }();
-    static const bool buf_off = [] {
-        const char *e = getenv("EDV_GEMM_BUF");  // 0: flat 64-bit DMA source addresses as in round 1 (A/B runs)
-        return e && atoi(e) == 0;
-    }();
+    static const bool buf_off = env_int("EDV_GEMM_BUF", 1) == 0;  // 0: flat 64-bit DMA source addresses as in round 1 (A/B runs)
     const bool buf = !buf_off && fits_buffer(d);
-    GemmSplit sp{1, 1, 0, 1, 0, nullptr, nullptr};
-    long long grid = tiles;
+    const SplitPolicy &pol = gemm_dma_split_policy();
+    GemmSplit sp{};
+    long long grid;
+    plan_plain(tiles, pol, &sp, &grid);
     const int slots = dma_slots<STORE, EP>();
     EDV_CHECK(slots > 0 && slots <= MAX_COUNTERS, "occupancy query failed");
-    const long long left = tiles % slots;
-    // worth splitting only when the grid is a few rounds deep (beyond ~5 the last round is a small fraction and the persistent
-    // form's 1-2 % deficit outweighs it: ViT-L fc2 at T=32, 10.7 rounds, measures -2 %)
-    static const int min_kt = [] {
-        const char *e = getenv("EDV_GEMM_SPLIT_MIN_KT");  // k-tiles per tile from which the split is used (A/B runs)
-        return e ? atoi(e) : 24;
-    }();
-    // ... and the tiles are deep: statically assigned persistent workgroups lose 1-10 % against the hardware's dynamic dispatch
-    // of the plain grid when a tile is only 12 k-tiles long (K = 384), and win 5-15 % from K = 768 up (warm A/B in
-    // profiles/r01_gemm_tile_sweep.txt)
-    static const int max_rounds = [] {
-        const char *e = getenv("EDV_GEMM_SPLIT_MAX_ROUNDS");  // grids of at least this many rounds run plain (A/B runs)
-        return e && atoi(e) > 0 ? atoi(e) : 8;
-    }();
-    static const int min_tiles = [] {
-        const char *e = getenv("EDV_GEMM_SPLIT_MIN_TILES");  // smaller grids run plain (A/B runs)
-        return e ? atoi(e) : 16;
-    }();
-    // small grids with deep tiles gain the most: 46 tiles x 48 k-tiles 33.7 -> 16.1 us, the C = 384 motion module's ff.net.2 (276 tiles) 57.5 -> 40.0
-    if (d.ws && !plain_forced && left > 0 && tiles > min_tiles && tiles < (long long)max_rounds * slots &&
-        d.K / DBK >= min_kt) {
-        const int nkt = d.K / DBK;
-        sp.whole_rounds = (int)(tiles / slots);
-        long long split_tiles = left;
-        // run length: an even share of the units over ALL workgroups.  When the leftover is too small for that (an even share would
-        // be under 1/4 of a tile's k range, i.e. a handful of workgroups would carry the whole tail and the merge would chain up to
-        // ~5 L2-bypassing loads at the very end of the launch), one whole round joins the split set instead: every workgroup then
-        // runs whole_rounds - 1 whole tiles plus 1 + left/slots tiles' worth of k-tiles, and every split tile has 2-3 pieces.
-        static const bool widen = [] {
-            const char *e = getenv("EDV_GEMM_SPLIT_WIDEN");  // 0: never move a whole round into the split set (A/B runs)
-            return !(e && atoi(e) == 0);
-        }();
-        const long long chunk_min = (nkt + 3) / 4;
-        if (widen && sp.whole_rounds > 0 && (left * nkt + slots - 1) / slots < chunk_min && left + slots <= MAX_COUNTERS) {
-            --sp.whole_rounds;
-            split_tiles += slots;
-        }
-        sp.units = split_tiles * nkt;
-        long long chunk = (sp.units + slots - 1) / slots;
-        chunk = chunk > chunk_min ? chunk : chunk_min;
-        sp.chunk = (int)chunk;
-        sp.nsplit = (int)((sp.units + chunk - 1) / chunk);
-        grid = sp.whole_rounds ? slots : (sp.nsplit > 0 ? sp.nsplit : 1);
-        sp.stride = (int)(grid / sp.nsplit) > 0 ? (int)(grid / sp.nsplit) : 1;
-        sp.cnt = reinterpret_cast<int *>(d.ws);
-        sp.ws = d.ws + MAX_COUNTERS;
-        EDV_CHECK((size_t)MAX_COUNTERS + (size_t)sp.nsplit * 2 * SLOT <= d.ws_floats && (uintptr_t)d.ws % 16 == 0,
-                  "stream-K workspace too small (gemm_workspace)");
-        if (buf && d.a_map.period == 0) EDV_LAUNCH((gemm_dma_kernel<STORE, EP, true, 2>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
-        else if (buf) EDV_LAUNCH((gemm_dma_kernel<STORE, EP, true, 1>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
-        else EDV_LAUNCH((gemm_dma_kernel<STORE, EP, true, 0>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
-        EDV_LAUNCH_OK();
-        return 0;
+    if (d.ws && !gemm_plain_forced() && plan_split(tiles, slots, d.K / DBK, pol, &sp, &grid)) {
+        split_bind(&sp, d.ws, pol);
+        EDV_CHECK(split_ws_floats(sp, pol) <= d.ws_floats && (uintptr_t)d.ws % 16 == 0, "stream-K workspace too small (gemm_workspace)");
+        launch_variant<STORE, EP, true>(d, sp, buf, grid, st);
+    } else {
+        launch_variant<STORE, EP, false>(d, sp, buf, grid, st);
     }
-    if (buf && d.a_map.period == 0) EDV_LAUNCH((gemm_dma_kernel<STORE, EP, false, 2>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
-    else if (buf) EDV_LAUNCH((gemm_dma_kernel<STORE, EP, false, 1>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
-    else EDV_LAUNCH((gemm_dma_kernel<STORE, EP, false, 0>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
     EDV_LAUNCH_OK();
     return 0;
 }
 
 // GEGLU epilogue (EP = 6): shallow tiles (K = C of a motion module), always the plain grid, buffer descriptors only (gemm_geglu_supported)
 int launch_geglu(const GemmDesc &d, long long tiles, hipStream_t st) {
-    const GemmSplit sp{1, 1, 0, 1, 0, nullptr, nullptr};
-    if (d.a_map.period == 0) EDV_LAUNCH((gemm_dma_kernel<STORE_ROWS, 6, false, 2>), dim3((unsigned)tiles), dim3(256), 0, st, d, sp);
-    else EDV_LAUNCH((gemm_dma_kernel<STORE_ROWS, 6, false, 1>), dim3((unsigned)tiles), dim3(256), 0, st, d, sp);
+    GemmSplit sp{};
+    long long grid;
+    plan_plain(tiles, gemm_dma_split_policy(), &sp, &grid);
+    if (d.a_map.period == 0) EDV_LAUNCH((gemm_dma_kernel<STORE_ROWS, 6, false, 2>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
+    else EDV_LAUNCH((gemm_dma_kernel<STORE_ROWS, 6, false, 1>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
     EDV_LAUNCH_OK();
     return 0;
 }
 
 }  // namespace
+
+// Which launches split.  Worth it only when the grid is a few rounds deep (beyond ~5 the last round is a small fraction and the persistent
+// form's 1-2 % deficit outweighs it: ViT-L fc2 at T=32, 10.7 rounds, measures -2 %) and the tiles are deep: statically assigned persistent
+// workgroups lose 1-10 % against the hardware's dynamic dispatch of the plain grid when a tile is only 12 k-tiles long (K = 384), and win
+// 5-15 % from K = 768 up (warm A/B in profiles/r01_gemm_tile_sweep.txt).  Small grids with deep tiles gain the most: 46 tiles x 48 k-tiles
+// 33.7 -> 16.1 us, the C = 384 motion module's ff.net.2 (276 tiles) 57.5 -> 40.0.
+const SplitPolicy &gemm_dma_split_policy() {
+    static const int max_rounds = env_int("EDV_GEMM_SPLIT_MAX_ROUNDS", 8);
+    static const SplitPolicy p{.min_kt = env_int("EDV_GEMM_SPLIT_MIN_KT", 24),        // k-tiles per tile from which the split is used (A/B runs)
+                               .min_tiles = env_int("EDV_GEMM_SPLIT_MIN_TILES", 16),  // smaller grids run plain (A/B runs)
+                               .max_rounds = max_rounds > 0 ? max_rounds : 8,         // grids of at least this many rounds run plain (A/B runs)
+                               .widen = env_int("EDV_GEMM_SPLIT_WIDEN", 1) != 0,      // 0: never move a whole round into the split set (A/B runs)
+                               .counters = MAX_COUNTERS, .slot_floats = SLOT, .whole_rounds = true};
+    return p;
+}
 
 size_t gemm_workspace() {
     int dev = 0, cus = 0;

@@ -16,7 +16,7 @@
 //
 // Tile 128 x 128, 16 k per stage, 3 stages of 24 KB (two workgroups per CU), 4 waves each holding 64 x 64 (2 x 2 accumulators).  W DMA and the A loads run
 // two stages ahead.  LDS plane image: 32-byte rows, the two 16-byte halves of row r swapped when (r >> 3) & 1, so a 16-lane ds_read_b128 group covers all
-// 64 banks.  Work split: the stream-K scheme of gemm_dma.hip (whole rounds of tiles, the leftover round cut along k into runs, the last arriver of a tile
+// 64 banks.  Work split: the stream-K scheme of streamk_plan.hpp / gemm_common.hpp (whole rounds of tiles, the leftover round cut along k into runs, the last arriver of a tile
 // merges the pieces in run order and applies the epilogue) with 128 x 128 pieces.
 //
 // Used for the encoder's linears in inference (engine.hip: Run::linear picks it when the weight has planes and the context computes in
@@ -84,9 +84,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
     }
 
     const int tile_l0 = sp.whole_rounds * G;
-    const int run = (SPLIT && sp.units > 0 && bid % sp.stride == 0 && bid / sp.stride < sp.nsplit) ? bid / sp.stride : -1;
-    long long u = run >= 0 ? (long long)run * sp.chunk : 0;
-    const long long u_end = run >= 0 ? (u + sp.chunk < sp.units ? u + sp.chunk : sp.units) : 0;
+    const int run = split_run(sp, SPLIT, bid);
+    long long u = split_run_begin(sp, run);
+    const long long u_end = split_run_end(sp, run, u);
     int round = 0;
     for (;;) {
         int tile, kt0, kt1, lt = 0;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
             kt1 = kt0 + left < nkt ? kt0 + (int)left : nkt;
             tile = tile_l0 + t;
             lt = t;
-            if (!(kt0 == 0 && kt1 == nkt)) part = sp.ws + ((long long)run * 2 + (u == (long long)run * sp.chunk ? 0 : 1)) * XSLOT;
+            if (!(kt0 == 0 && kt1 == nkt)) part = split_slot<XSLOT>(sp, run, u);  // a piece: not the tile's whole k range
             u += kt1 - kt0;
         } else {
             break;
@@ -298,8 +298,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
         EDV_X6_STAMP(2);
         bool store_tile = true;
         if (SPLIT && part) {
-            // piece hand-off: the protocol of gemm_dma.hip (sc1 stores, every wave's vmcnt(0), barrier, one agent-scope counter add; the last arriver
-            // acquires, then reads every piece with sc1 loads in run order)
+            // piece hand-off (gemm_common.hpp: sc1 stores, every wave's vmcnt(0), barrier, one agent-scope counter add; the last arriver acquires,
+            // then reads every piece with sc1 loads in run order)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -308,20 +308,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
                     for (int r = 0; r < 16; ++r)
                         __hip_atomic_store(&part[((wave * 4 + i * 2 + j) * 16 + r) * 64 + lane], acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const long long ub = (long long)lt * nkt;
-            const int g0 = (int)(ub / sp.chunk), g1 = (int)((ub + nkt - 1) / sp.chunk);
-            int *s_last = reinterpret_cast<int *>(smem);  // all stages are idle between the k loop and the next run's first DMA
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                const int arrived = __hip_atomic_fetch_add(&sp.cnt[lt], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int last = arrived == g1 - g0;
-                if (last) __hip_atomic_store(&sp.cnt[lt], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (last) split_merge_acquire();
-                *s_last = last;
-            }
-            __syncthreads();
-            store_tile = *s_last != 0;
-            __syncthreads();
+            int g0, g1;
+            store_tile = split_handoff(sp, &sp.cnt[lt], ub, nkt, reinterpret_cast<int *>(smem), tid, g0, g1);  // all stages are idle here
             if (store_tile) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -330,7 +318,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
 #pragma unroll
                         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
                 for (int gg = g0; gg <= g1; ++gg) {  // run order, whatever the arrival order was
-                    const float *pp = sp.ws + ((long long)gg * 2 + ((long long)gg * sp.chunk >= ub ? 0 : 1)) * XSLOT + (wave * 4 * 16) * 64 + lane;
+                    const float *pp = split_piece<XSLOT>(sp.ws, sp, gg, ub) + (wave * 4 * 16) * 64 + lane;
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -364,62 +352,25 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
 template <int ACT>
 int x6_slots() {
     static DeviceSlotCache cache;
-    return cache.get([] {
-        int dev = 0, cus = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipFuncSetAttribute((const void *)gemm_x6_kernel<ACT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, XNST * XSTAGE) != hipSuccess) return 0;
-        if (hipFuncSetAttribute((const void *)gemm_x6_kernel<ACT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, XNST * XSTAGE) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_x6_kernel<ACT, true>, 256, XNST * XSTAGE) != hipSuccess) return 0;
-        if (per_cu > 2) per_cu = 2;  // 2 x 72 KB of LDS
-        if (const char *e = getenv("EDV_X6_SLOTS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
-        if (getenv("EDV_DEBUG_SLOTS")) fprintf(stderr, "gemm_x6_kernel<%d>: %d CUs x %d resident workgroups\n", ACT, cus, per_cu);
-        return cus * per_cu;
-    });
+    static const std::string label = "gemm_x6_kernel<" + std::to_string(ACT) + ">";
+    // at most 2: 2 x 72 KB of LDS.  (The plain instantiation is launched with the same dynamic LDS size and opts into it here too.)
+    return resident_workgroups(cache, (const void *)gemm_x6_kernel<ACT, true>, 256, XNST * XSTAGE, 2, "EDV_X6_SLOTS_PER_CU", label.c_str(),
+                               (const void *)gemm_x6_kernel<ACT, false>);
 }
 
 template <int ACT>
 int launch_x6(const GemmDesc &d, long long tiles, hipStream_t st) {
-    static const bool plain_forced = [] {
-        const char *e = getenv("EDV_GEMM_PLAIN");
-        return e && atoi(e) != 0;
-    }();
-    GemmSplit sp{1, 1, 0, 1, 0, nullptr, nullptr};
-    static const int group_m = [] {
-        const char *e = getenv("EDV_X6_GROUP_M");  // row blocks per tile group (A/B runs); 1 = row-major tile order
-        return e && atoi(e) > 0 ? atoi(e) : 8;
-    }();
-    sp.group_m = group_m;
-    long long grid = tiles;
+    const SplitPolicy &pol = gemm_x6_split_policy();
+    GemmSplit sp{};
+    static const int group_m = env_int("EDV_X6_GROUP_M", 8);  // row blocks per tile group (A/B runs); 1 = row-major tile order
+    sp.group_m = group_m > 0 ? group_m : 8;
+    long long grid;
+    plan_plain(tiles, pol, &sp, &grid);
     const int slots = x6_slots<ACT>();
     EDV_CHECK(slots > 0 && slots <= XMAX_COUNTERS, "occupancy query failed");
-    const long long left = tiles % slots;
-    const int nkt = d.K / XBK;
-    // The split pays from K = 768 up (fc2 at T = 8: 110 -> 93 us); at K = 384 a tile is 24 steps, the pieces and their merge cost more than the uneven
-    // last round, and the plain grid's dynamic dispatch wins (qkv 87 -> 78 us, proj 40 -> 35 us; profiles/r03_gemm_x6_shapes.txt).  Launching every
-    // workgroup pair of a CU in lockstep is not what costs: alternating the order of whole tiles and runs between workgroups changed nothing.
-    static const int min_kt = [] {
-        const char *e = getenv("EDV_X6_SPLIT_MIN_KT");  // k-steps per tile from which the split is used (A/B runs)
-        return e ? atoi(e) : 48;
-    }();
-    if (d.ws && !plain_forced && left > 0 && tiles > 16 && tiles < 8ll * slots && nkt >= min_kt) {
-        sp.whole_rounds = (int)(tiles / slots);
-        long long split_tiles = left;
-        const long long chunk_min = (nkt + 3) / 4;
-        if (sp.whole_rounds > 0 && (left * nkt + slots - 1) / slots < chunk_min && left + slots <= XMAX_COUNTERS) {
-            --sp.whole_rounds;
-            split_tiles += slots;
-        }
-        sp.units = split_tiles * nkt;
-        long long chunk = (sp.units + slots - 1) / slots;
-        chunk = chunk > chunk_min ? chunk : chunk_min;
-        sp.chunk = (int)chunk;
-        sp.nsplit = (int)((sp.units + chunk - 1) / chunk);
-        grid = sp.whole_rounds ? slots : (sp.nsplit > 0 ? sp.nsplit : 1);
-        sp.stride = (int)(grid / sp.nsplit) > 0 ? (int)(grid / sp.nsplit) : 1;
-        sp.cnt = reinterpret_cast<int *>(d.ws);
-        sp.ws = d.ws + XMAX_COUNTERS;
-        EDV_CHECK((size_t)XMAX_COUNTERS + (size_t)sp.nsplit * 2 * XSLOT <= d.ws_floats && (uintptr_t)d.ws % 16 == 0, "stream-K workspace too small (gemm_workspace)");
+    if (d.ws && !gemm_plain_forced() && plan_split(tiles, slots, d.K / XBK, pol, &sp, &grid)) {
+        split_bind(&sp, d.ws, pol);
+        EDV_CHECK(split_ws_floats(sp, pol) <= d.ws_floats && (uintptr_t)d.ws % 16 == 0, "stream-K workspace too small (gemm_workspace)");
         EDV_LAUNCH((gemm_x6_kernel<ACT, true>), dim3((unsigned)grid), dim3(256), XNST * XSTAGE, st, d, sp);
         EDV_LAUNCH_OK();
         return 0;
@@ -430,6 +381,15 @@ int launch_x6(const GemmDesc &d, long long tiles, hipStream_t st) {
 }
 
 }  // namespace
+
+// The split pays from K = 768 up (fc2 at T = 8: 110 -> 93 us); at K = 384 a tile is 24 steps, the pieces and their merge cost more than the uneven
+// last round, and the plain grid's dynamic dispatch wins (qkv 87 -> 78 us, proj 40 -> 35 us; profiles/r03_gemm_x6_shapes.txt).  Launching every
+// workgroup pair of a CU in lockstep is not what costs: alternating the order of whole tiles and runs between workgroups changed nothing.
+const SplitPolicy &gemm_x6_split_policy() {
+    static const SplitPolicy p{.min_kt = env_int("EDV_X6_SPLIT_MIN_KT", 48),  // k-steps per tile from which the split is used (A/B runs)
+                               .min_tiles = 16, .max_rounds = 8, .widen = true, .counters = XMAX_COUNTERS, .slot_floats = XSLOT, .whole_rounds = true};
+    return p;
+}
 
 size_t gemm_x6_planes_bytes(int N, int K) { return (size_t)3 * N * K * 2; }
 

@@ -2,6 +2,7 @@
 // pointers; every function enqueues on `st` and returns 0 / non-zero (text via edv::get_error()).
 #pragma once
 #include "common.hpp"
+#include "streamk_plan.hpp"
 
 namespace edv {
 
@@ -72,6 +73,10 @@ int gemm_dma(const GemmDesc &d, hipStream_t st);
 // LDS-DMA implicit-GEMM 3x3 convolution (conv_dma.hip): Cin % 32 == 0, any stride the GemmDesc allows
 bool conv_dma_supported(const GemmDesc &d);
 int conv_dma(const GemmDesc &d, hipStream_t st);
+// the split policies the three launchers above run with (streamk_plan.hpp); edv_split_plan runs the planner on them without a device
+const SplitPolicy &gemm_dma_split_policy();
+const SplitPolicy &gemm_x6_split_policy();
+const SplitPolicy &conv_dma_split_policy();
 // flops of the last-launched gemm tile choice, for the bench's roofline bookkeeping
 const char *gemm_kernel_name(const GemmDesc &d);
 

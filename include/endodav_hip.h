@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define EDV_ABI_VERSION 14 /* 14: evaluation on the device (edv_metrics_workspace, edv_masked_median, edv_metrics_pred, edv_metrics_errors, edv_metrics_temporal); 13: test entry points for row-mapped GEMM / LayerNorm descriptors and the folds (edv_gemm_desc ... edv_bilinear_add); 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
+#define EDV_ABI_VERSION 15 /* 15: edv_split_plan (test entry point: the stream-K planners without a device); 14: evaluation on the device (edv_metrics_workspace, edv_masked_median, edv_metrics_pred, edv_metrics_errors, edv_metrics_temporal); 13: test entry points for row-mapped GEMM / LayerNorm descriptors and the folds (edv_gemm_desc ... edv_bilinear_add); 12: edv_stitch_fit, edv_stitch_apply; 11: edv_set_bias_grads, edv_colsum_batch; 9: edv_trainer_loss; 8: edv_debug_fill_lds (test hook); 7: the split-bf16 experiment entry points left the library */
 
 enum edv_lora_type { EDV_LORA_NONE = 0, EDV_LORA_LORA = 1, EDV_LORA_DVLORA = 2, EDV_LORA_SSB = 3, EDV_LORA_DASH = 4 };
 
@@ -527,6 +527,13 @@ int edv_sigmoid_bwd(const float *g_dev, const float *s_dev, float *out_dev, int6
 /* edv_bilinear plus an addend shaped like the output (C % 4 == 0): y = up(x) + add. */
 int edv_bilinear_add(const float *x_dev, const float *add_dev, float *y_dev, int32_t F, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
                      void *stream);
+
+/* ---- test entry point (ABI 15): the host planner of the persistent stream-K grids, with `slots` (resident workgroups) given instead of
+ * queried.  Touches no device.  kind: 0 LDS-DMA GEMM, 1 bf16x6 GEMM, 2 3x3 convolution (tiles of k_tiles k-tiles), 3 spatial attention
+ * forward / backward (tasks of k_tiles key tiles).  It runs the launch path's own policy (environment knobs included) as for a launch with
+ * a workspace.  out = { 1 split / 0 plain, grid, whole_rounds, chunk, nsplit, stride (kind 3: leftover tasks), units,
+ * workspace floats the plan needs (kinds 0-2; kind 3: pieces, to be multiplied by the caller's rows x columns) }. */
+int edv_split_plan(int32_t kind, int64_t tiles_or_tasks, int32_t slots, int32_t k_tiles, int64_t out[8]);
 
 #ifdef __cplusplus
 }

@@ -43,11 +43,11 @@ def test_ref64_agrees_with_the_host_metrics_and_the_known_answers():
 
 # ---- 2. the ABI ---------------------------------------------------------------------------------------------------------------------------
 def test_abi_14_types_the_metrics_entry_points():
-    assert _lib.ABI_VERSION == 14
+    assert _lib.ABI_VERSION == 15
     for name in NEW_ENTRY_POINTS:
         assert name in _lib.SIGNATURES, name
     lib = _lib.load()
-    assert lib.edv_abi_version() == 14
+    assert lib.edv_abi_version() == 15
     head = lib.edv_metrics_workspace(0, 0, 0)
     assert head > 0
     # the key images of one chunk of pairs are all that depends on the shape, and nothing depends on the length of the clip

@@ -11,7 +11,7 @@ import torch.nn.functional as F
 from endodav_amd import _lib
 
 pytestmark = pytest.mark.gpu
-COUNTER_FLOATS = 4096  # MAX_COUNTERS of gemm_dma.hip
+COUNTER_FLOATS = 4096  # SPLIT_MAX_COUNTERS of gemm_common.hpp
 
 
 def st():
