@@ -132,6 +132,8 @@ SIGNATURES = {
     "edv_patchify": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.c_void_p]),
     "edv_bicubic_pos": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _f64, _f64, C.c_void_p]),
     "edv_resize_bicubic": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.c_void_p]),
+    # additive entry point (ABI stays 15): uint8 frames -> the network's input; the slots are host memory, NULL = identity
+    "edv_ingest_u8": (C.c_int, [_fp, _i32, C.POINTER(_i32), _i32, _fp, _i32, _i32, _i32, _i32, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

@@ -254,6 +254,11 @@ int edv_resize_bicubic(const float *x_dev, float *y_dev, int32_t planes, int32_t
     return resize_bicubic(x_dev, y_dev, planes, H, W, OH, OW, (hipStream_t)stream);
 }
 
+int edv_ingest_u8(const uint8_t *src_dev, int32_t src_frames, const int32_t *slots_host, int32_t n, float *out_dev, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                  void *stream) {
+    return ingest_u8(src_dev, src_frames, slots_host, n, out_dev, H, W, OH, OW, (hipStream_t)stream);
+}
+
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream) {

@@ -115,6 +115,9 @@ int cls_rows(const float *cls, const float *pos, float *tokens, int F, int ntok,
 int sigmoid_inplace(float *x, long long n, hipStream_t st);
 // planar bicubic image resize (cv2.INTER_CUBIC semantics) for infer_video_depth's pre-resize
 int resize_bicubic(const float *x, float *y, int NP, int H, int W, int OH, int OW, hipStream_t st);
+// frames slots[0..n) of src [src_frames, H, W, 3] uint8 -> out [n, 3, OH, OW] in [0, 1], resized as by resize_bicubic when (OH, OW) != (H, W);
+// slots_host: host memory, NULL = 0..n-1; 1 <= n <= 64.  Bit-identical to torch's .to(float32).div_(255.0), made planar, followed by resize_bicubic.
+int ingest_u8(const uint8_t *src, int src_frames, const int32_t *slots_host, int n, float *out, int H, int W, int OH, int OW, hipStream_t st);
 // whole-video stitching on the device (stitch.hip): disp [32, ih, iw] is upsampled to [fh, fw] on the fly; st = (s, t) in device memory
 size_t stitch_workspace();  // bytes
 int stitch_fit(const float *disp, int ih, int iw, const float *tail, int fh, int fw, float *st, void *ws, size_t ws_bytes, hipStream_t stream);

@@ -169,6 +169,36 @@ __device__ __forceinline__ void cubic_source(int o, int n, int on, int &i0, floa
     t = (float)r / (float)den;
 }
 
+// The 16-tap blend of output pixel (oy, ox) for NC values per source pixel that share the tap weights and the clamped tap addresses:
+// `load(off, v)` fills v[NC] with the samples at pixel offset off = yy * W + xx.  One sequence of rounded products and sums per value.
+template <int NC, class Load>
+__device__ __forceinline__ void cubic_blend(int oy, int ox, int H, int W, int OH, int OW, Load load, float (&acc)[NC]) {
+    int iy, ix;
+    float ty, tx;
+    cubic_source(oy, H, OH, iy, ty);
+    cubic_source(ox, W, OW, ix, tx);
+    const float wy[4] = {cc2(ty + 1.f), cc1(ty), cc1(1.f - ty), cc2(2.f - ty)};
+    const float wx[4] = {cc2(tx + 1.f), cc1(tx), cc1(1.f - tx), cc2(2.f - tx)};
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int yy = min(max(iy - 1 + a, 0), H - 1);
+        float rowv[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) rowv[c] = 0.f;
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb) {
+            float v[NC];
+            load((long long)yy * W + min(max(ix - 1 + bb, 0), W - 1), v);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) rowv[c] += wx[bb] * v[c];
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) acc[c] += wy[a] * rowv[c];
+    }
+}
+
 // planar image resize with the same cubic (cv2.INTER_CUBIC / ATen bicubic, align_corners=False)
 __global__ void resize_bicubic_kernel(const float *__restrict__ x, float *__restrict__ y, int NP, int H, int W, int OH, int OW) {
     const long long total = (long long)NP * OH * OW;
@@ -176,23 +206,48 @@ __global__ void resize_bicubic_kernel(const float *__restrict__ x, float *__rest
         const int ox = (int)(i % OW);
         const int oy = (int)((i / OW) % OH);
         const long long pl = i / ((long long)OW * OH);
-        int iy, ix;
-        float ty, tx;
-        cubic_source(oy, H, OH, iy, ty);
-        cubic_source(ox, W, OW, ix, tx);
-        const float wy[4] = {cc2(ty + 1.f), cc1(ty), cc1(1.f - ty), cc2(2.f - ty)};
-        const float wx[4] = {cc2(tx + 1.f), cc1(tx), cc1(1.f - tx), cc2(2.f - tx)};
         const float *src = x + pl * H * W;
-        float acc = 0.f;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int yy = min(max(iy - 1 + a, 0), H - 1);
-            float rowv = 0.f;
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) rowv += wx[bb] * src[(long long)yy * W + min(max(ix - 1 + bb, 0), W - 1)];
-            acc += wy[a] * rowv;
-        }
-        y[i] = acc;
+        float acc[1];
+        cubic_blend<1>(oy, ox, H, W, OH, OW, [src](long long off, float (&v)[1]) { v[0] = src[off]; }, acc);
+        y[i] = acc[0];
+    }
+}
+
+// Frame ingest of streamed video: uint8 HWC frames -> [0, 1] fp32 planar CHW, bicubically resized when RESIZE.  The conversion is
+// ATen's for `.to(float32).div_(255.0)` on the device: division by a host scalar multiplies by the fp32 reciprocal (rounded on the host),
+// which differs from v / 255.f in the last bit for some bytes; tests/test_ingest_gpu.py holds all 256 values to torch's.
+struct IngestSlots {
+    int32_t s[64];  // by value in the launch: no upload, no device allocation
+};
+
+__device__ __forceinline__ float unit_from_u8(uint8_t b) { return (float)b * (1.0f / 255.0f); }
+
+// thread per output pixel, all three channels: the tap weights and addresses are shared, the three bytes of a source pixel are adjacent
+// (byte loads: a row stride of W * 3 bytes is not 4-byte aligned in general), and each of the three plane stores is coalesced across lanes
+template <bool RESIZE>
+__global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t *__restrict__ src, IngestSlots slots, float *__restrict__ out, int n, int H, int W,
+                                                         int OH, int OW) {
+    const long long plane = (long long)OH * OW, total = (long long)n * plane;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int ox = (int)(i % OW);
+        const int oy = (int)((i / OW) % OH);
+        const long long f = i / plane;
+        const uint8_t *fr = src + (long long)slots.s[f] * H * W * 3;
+        float acc[3];
+        auto load = [fr](long long off, float (&v)[3]) {
+            const uint8_t *p = fr + off * 3;
+            v[0] = unit_from_u8(p[0]);
+            v[1] = unit_from_u8(p[1]);
+            v[2] = unit_from_u8(p[2]);
+        };
+        if (RESIZE)
+            cubic_blend<3>(oy, ox, H, W, OH, OW, load, acc);
+        else
+            load((long long)oy * W + ox, acc);
+        float *o = out + f * 3 * plane + (long long)oy * OW + ox;
+        o[0] = acc[0];
+        o[plane] = acc[1];
+        o[2 * plane] = acc[2];
     }
 }
 
@@ -269,6 +324,26 @@ int resize_bicubic(const float *x, float *y, int NP, int H, int W, int OH, int O
     EDV_CHECK(x && y && NP > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "bad operand");
     EDV_CHECK(2ll * OH * H + OH < (1ll << 31) && 2ll * OW * W + OW < (1ll << 31), "resize_bicubic: input size x output size beyond 2^30 per axis");
     EDV_LAUNCH(resize_bicubic_kernel, dim3(grid_for((long long)NP * OH * OW, 16384)), dim3(256), 0, st, x, y, NP, H, W, OH, OW);
+    EDV_LAUNCH_OK();
+    return 0;
+}
+
+int ingest_u8(const uint8_t *src, int src_frames, const int32_t *slots_host, int n, float *out, int H, int W, int OH, int OW, hipStream_t st) {
+    EDV_CHECK(src && out, "ingest_u8: null operand");
+    EDV_CHECK(src_frames > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "ingest_u8: empty problem");
+    EDV_CHECK(n >= 1 && n <= 64, "ingest_u8: n must be 1..64 (the slots travel by value in the launch)");
+    EDV_CHECK(2ll * OH * H + OH < (1ll << 31) && 2ll * OW * W + OW < (1ll << 31), "ingest_u8: input size x output size beyond 2^30 per axis");
+    IngestSlots slots = {};
+    for (int i = 0; i < n; ++i) {
+        slots.s[i] = slots_host ? slots_host[i] : i;
+        EDV_CHECK(slots.s[i] >= 0 && slots.s[i] < src_frames, "ingest_u8: slot outside [0, src_frames)");
+    }
+    const int grid = grid_for((long long)n * OH * OW, 16384);
+    if (OH == H && OW == W) {
+        EDV_LAUNCH(ingest_u8_kernel<false>, dim3(grid), dim3(256), 0, st, src, slots, out, n, H, W, OH, OW);
+    } else {
+        EDV_LAUNCH(ingest_u8_kernel<true>, dim3(grid), dim3(256), 0, st, src, slots, out, n, H, W, OH, OW);
+    }
     EDV_LAUNCH_OK();
     return 0;
 }

@@ -827,3 +827,12 @@ class endodav(nn.Module):
         from .video import infer_video_depth as _impl
 
         return _impl(self, frames, input_size=input_size, device=device, shard_windows=shard_windows, stitch=stitch, output=output)
+
+    def stream_video_depth(self, frame_shape, device="cuda", output="host"):
+        """``infer_video_depth(stitch="device")`` for a live feed (not in the reference): returns a ``video.DepthStream`` whose
+        ``push(chunk)`` takes uint8 frames [m, H, W, 3] as they arrive and returns the float32 depth [r, H, W] of the frames that became
+        final, and whose ``close()`` returns the rest.  Whatever the chunking, the concatenation equals the offline result bit for bit.
+        Depth lags the newest frame by at most 29 frames between windows (the reference's 32-frame windows with an 8-frame cross-fade)."""
+        from .video import DepthStream
+
+        return DepthStream(self, frame_shape, device=device, output=output)

@@ -118,6 +118,82 @@ def window_sources(n_frames: int) -> List[np.ndarray]:
     return out
 
 
+def _video_lanes(model, dev: torch.device):
+    """(dash, depth, flight) of the video paths: the model's cached ``_video_flight`` (built once: a lane's engine context holds packed weights
+    and a workspace), shared by ``HipWindowRunner`` and ``DepthStream``.
+    A lora_type="dash" model counts its forwards (one DashLinear call counter per model, switched on after 100 calls) and so has one
+    engine context only: its windows run one at a time on lane 0, on one stream, one _dash_step per window in window
+    order -- the reference's sequence of forward calls.  The copies still overlap the forward."""
+    from .pipeline import ClipsInFlight
+
+    dash = getattr(model, "lora_type", None) == "dash"
+    depth = 1 if dash else ClipsInFlight.auto_depth(model, INFER_LEN)
+    flight = None if dash else getattr(model, "_video_flight", None)
+    if not dash and (flight is None or flight.dev != dev or flight.depth != depth):
+        flight = ClipsInFlight(model, dev, depth=depth)
+        try:
+            model._video_flight = flight
+        except Exception:
+            pass
+    return dash, depth, flight
+
+
+def _pre_resize(lib, cur: torch.Tensor, fh: int, fw: int, th: int, tw: int, st) -> torch.Tensor:
+    """The pre-resize step of ``HipWindowRunner._run_windows``, shared with ``DepthStream`` so that both feed the forward the same bits:
+    ``cur`` is the window's converted frames (``permute -> float32 -> div_(255.0)``, in the memory layout ``.to`` leaves it in)."""
+    if (th, tw) == (fh, fw):
+        return cur
+    small = torch.empty((INFER_LEN, 3, th, tw), device=cur.device, dtype=torch.float32)
+    _lib.check(lib.edv_resize_bicubic(cur.data_ptr(), small.data_ptr(), INFER_LEN * 3, fh, fw, th, tw, st), "edv_resize_bicubic")
+    return small
+
+
+class _DeviceStitch:
+    """The state of the device stitch, shared by ``HipWindowRunner.run_stitched`` and ``DepthStream``: two frame-size buffers [32, fh, fw] that
+    alternate between the windows (the 8-frame tail window k is fitted against is the end of window k-1's buffer), (s, t) and the workspace
+    of edv_stitch_fit, and ``done``, the number of output frames handed out as final.  After window k the output has 32 + 22 k frames of
+    which all but the last 8 are final; window 0 holds frames 0..31, window k >= 1 frames 22 k + 10 .. 22 k + 31."""
+
+    def __init__(self, lib, dev: torch.device, fh: int, fw: int, nbuf: int = 2):
+        self.lib, self.fh, self.fw = lib, fh, fw
+        self.ring = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        self.st = torch.empty(2, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(int(lib.edv_stitch_workspace()), dtype=torch.uint8, device=dev)
+        self.done = 0
+
+    def window(self, k: int, disp: torch.Tensor, s_st: torch.cuda.Stream) -> None:
+        """Fit and apply window k's network-size disparity [32, 1, ih, iw]; called under ``torch.cuda.stream(s_st)``, in window order, once
+        ``s_st`` waits for the lane.  ``disp`` belongs to the lane's allocator pool: ``record_stream`` keeps it until ``s_st`` has read it."""
+        lib, fh, fw, ring = self.lib, self.fh, self.fw, self.ring
+        step = INFER_LEN - OVERLAP
+        st = C.c_void_p(s_st.cuda_stream)
+        disp = disp.contiguous()
+        ih, iw = disp.shape[-2], disp.shape[-1]
+        cur = ring[k % 2]
+        if k == 0:
+            _lib.check(lib.edv_stitch_apply(disp.data_ptr(), ih, iw, None, None, cur.data_ptr(), fh, fw, st), "edv_stitch_apply")
+        else:
+            tail = ring[(k - 1) % 2][(INFER_LEN if k == 1 else step) - INTERP_LEN:]
+            _lib.check(lib.edv_stitch_fit(disp.data_ptr(), ih, iw, tail.data_ptr(), fh, fw, self.st.data_ptr(), self.ws.data_ptr(), self.ws.numel(), st),
+                       "edv_stitch_fit")
+            _lib.check(lib.edv_stitch_apply(disp.data_ptr(), ih, iw, self.st.data_ptr(), tail.data_ptr(), cur.data_ptr(), fh, fw, st), "edv_stitch_apply")
+        disp.record_stream(s_st)
+
+    def final_pieces(self, upto: int) -> List[Tuple[int, torch.Tensor]]:
+        """[(g, frames g .. g + len - 1 as a view of a buffer)] covering output frames ``done`` .. ``upto`` - 1, in order, and ``done`` moves to
+        ``upto``: at most two pieces per window, the faded tail in window k-1's buffer, then window k's own frames."""
+        step = INFER_LEN - OVERLAP
+        pieces = []
+        g = self.done
+        while g < upto:
+            w, i = (0, g) if g < INFER_LEN else ((g - OVERLAP) // step, (g - OVERLAP) % step)
+            cnt = min(upto - g, (INFER_LEN if w == 0 else step) - i)
+            pieces.append((g, self.ring[w % 2][i:i + cnt]))
+            g += cnt
+        self.done = max(self.done, upto)
+        return pieces
+
+
 class HipWindowRunner:
     """Runs 32-frame windows of one video through the HIP forward, pipelined over copy streams and (round 3) up to three compute lanes:
 
@@ -141,8 +217,6 @@ class HipWindowRunner:
         ``begin(nbuf, entry)`` allocates the caller's buffers (``nbuf`` slots are in use at a time; ``entry``: see the stream contract below),
         ``before_forward(k, slot)`` runs on the host before window k is enqueued, ``after_forward(k, slot, stream, disp)`` under the lane's
         stream right after its forward: ``disp`` [32, 1, ih, iw] is the window's network-size disparity, valid in stream order."""
-        from .pipeline import ClipsInFlight
-
         lib = _lib.load()
         dev, fh, fw, th, tw = self.dev, self.fh, self.fw, self.th, self.tw
         with torch.cuda.device(dev), torch.no_grad():
@@ -150,18 +224,8 @@ class HipWindowRunner:
             # engine context and stream (pipeline.ClipsInFlight; depth by auto_depth: 3 lanes at the reference's 224 x 280, one at 518 x 518 where a
             # 32-frame window fills the part alone -- ViT-S 224 x 280 T=32: 4140 -> 4380..4760 frames/s, profiles/r03_notes.txt).  A lane's stream
             # carries the whole per-window chain: uint8 -> float, pre-resize, forward, resize back.
-            # A lora_type="dash" model counts its forwards (one DashLinear call counter per model, switched on after 100 calls) and so has one
-            # engine context only: its windows run one at a time on lane 0, on one stream of this runner, one _dash_step per window in window
-            # order -- the reference's sequence of forward calls.  The copies still overlap the forward.
-            dash = getattr(self.model, "lora_type", None) == "dash"
-            depth = 1 if dash else ClipsInFlight.auto_depth(self.model, INFER_LEN)
-            flight = None if dash else getattr(self.model, "_video_flight", None)  # kept with the model: a lane's engine context (packed weights, workspace) is built once
-            if not dash and (flight is None or flight.dev != dev or flight.depth != depth):
-                flight = ClipsInFlight(self.model, dev, depth=depth)
-                try:
-                    self.model._video_flight = flight
-                except Exception:
-                    pass
+            # A lora_type="dash" model runs its windows one at a time on lane 0, on one stream of this runner (_video_lanes).
+            dash, depth, flight = _video_lanes(self.model, dev)
             nbuf = min(depth + 1, len(sources))
             s_in = torch.cuda.Stream(device=dev)
             s_dash = torch.cuda.Stream(device=dev) if dash else None
@@ -205,10 +269,7 @@ class HipWindowRunner:
                     cur = d_in[slot].permute(0, 3, 1, 2).to(torch.float32).div_(255.0)  # [32, 3, H, W] in [0, 1]
                     used[slot] = torch.cuda.Event()
                     used[slot].record(stream)
-                    if (th, tw) != (fh, fw):
-                        small = torch.empty((INFER_LEN, 3, th, tw), device=dev, dtype=torch.float32)
-                        _lib.check(lib.edv_resize_bicubic(cur.data_ptr(), small.data_ptr(), INFER_LEN * 3, fh, fw, th, tw, st), "edv_resize_bicubic")
-                        cur = small
+                    cur = _pre_resize(lib, cur, fh, fw, th, tw, st)
                     disp = self.model(cur.unsqueeze(0), lane=lane)[("disp", 0)]  # [32, 1, ih, iw]
                     after_forward(k, slot, stream, disp)
 
@@ -282,43 +343,21 @@ class HipWindowRunner:
 
         def begin(nbuf: int, entry: torch.cuda.Event) -> None:
             s_st.wait_event(entry)
-            state["ring"] = [torch.empty((INFER_LEN, fh, fw), dtype=torch.float32, device=dev) for _ in range(min(2, len(sources)))]
-            state["st"] = torch.empty(2, dtype=torch.float32, device=dev)
-            state["ws"] = torch.empty(int(lib.edv_stitch_workspace()), dtype=torch.uint8, device=dev)
+            state["stitch"] = _DeviceStitch(lib, dev, fh, fw, min(2, len(sources)))
             # the device result comes from the caller's stream's pool and is first written on the stitch stream, which has waited for `entry`
             state["out"] = torch.empty((n_keep, fh, fw), dtype=torch.float32, device=dev) if on_device else torch.empty((n_keep, fh, fw), dtype=torch.float32, pin_memory=True)
 
-        def place(g: int) -> Tuple[int, int]:
-            """(window, index in that window's buffer) of output frame g: window 0 holds frames 0..31, window k >= 1 frames 22 k + 10 .. 22 k + 31."""
-            return (0, g) if g < INFER_LEN else ((g - OVERLAP) // step, (g - OVERLAP) % step)
-
         def after_forward(k: int, slot: int, stream: torch.cuda.Stream, disp: torch.Tensor) -> None:
-            ring, out = state["ring"], state["out"]
+            stitch, out = state["stitch"], state["out"]
             ready = torch.cuda.Event()
             ready.record(stream)
             with torch.cuda.stream(s_st):
                 s_st.wait_event(ready)
-                st = C.c_void_p(s_st.cuda_stream)
-                disp = disp.contiguous()
-                ih, iw = disp.shape[-2], disp.shape[-1]
-                cur = ring[k % 2]
-                if k == 0:
-                    _lib.check(lib.edv_stitch_apply(disp.data_ptr(), ih, iw, None, None, cur.data_ptr(), fh, fw, st), "edv_stitch_apply")
-                else:
-                    tail = ring[(k - 1) % 2][(INFER_LEN if k == 1 else step) - INTERP_LEN:]
-                    _lib.check(lib.edv_stitch_fit(disp.data_ptr(), ih, iw, tail.data_ptr(), fh, fw, state["st"].data_ptr(), state["ws"].data_ptr(),
-                                                  state["ws"].numel(), st), "edv_stitch_fit")
-                    _lib.check(lib.edv_stitch_apply(disp.data_ptr(), ih, iw, state["st"].data_ptr(), tail.data_ptr(), cur.data_ptr(), fh, fw, st),
-                               "edv_stitch_apply")
-                disp.record_stream(s_st)
+                stitch.window(k, disp, s_st)
                 upto = n_keep if k == last else min(n_keep, INFER_LEN + step * k - INTERP_LEN)
-                g = state["done"]
-                while g < upto:                       # at most two pieces: the faded tail in window k-1's buffer, then window k's own frames
-                    w, i = place(g)
-                    cnt = min(upto - g, (INFER_LEN if w == 0 else step) - i)
-                    out[g:g + cnt].copy_(ring[w % 2][i:i + cnt], non_blocking=True)
-                    g += cnt
-                state["done"] = max(state["done"], upto)
+                for g, piece in stitch.final_pieces(upto):
+                    out[g:g + piece.shape[0]].copy_(piece, non_blocking=True)
+                state["done"] = stitch.done
 
         self._run_windows(sources, begin, lambda k, slot: None, after_forward)
         s_st.synchronize()
@@ -395,3 +434,254 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
     if shards is None:
         return None
     return stitch_windows(parallel.merge_shards(shards, len(sources)), n)
+
+
+# ---------------------------------------------------------------------------------------------
+# streaming: frames are pushed as they arrive, depth comes back as soon as it is final
+# ---------------------------------------------------------------------------------------------
+STREAM_RING = 64  # frames the device ring holds; tests/test_stream_cpu.py derives the bound it must meet from window_sources
+
+
+def stream_trigger(k: int) -> int:
+    """Frames that must have arrived before window k can run: its last input frame is 22 k + 31.  For every n >= stream_trigger(k),
+    ``window_sources(n)[k]`` is the same (no padding reaches the window), so the window run then reproduces the offline one."""
+    return (INFER_LEN - OVERLAP) * k + INFER_LEN
+
+
+def stream_final(k: int) -> int:
+    """Output frames that are final once window k is stitched and is not the last one: all 32 + 22 k but the 8 the next window fades."""
+    return INFER_LEN + (INFER_LEN - OVERLAP) * k - INTERP_LEN
+
+
+def stream_next_source(k: int, prev: Optional[np.ndarray]) -> np.ndarray:
+    """``window_sources(n)[k]`` for any n >= stream_trigger(k), from window k-1's: one link of the key-frame chain."""
+    idx = np.arange((INFER_LEN - OVERLAP) * k, (INFER_LEN - OVERLAP) * k + INFER_LEN)
+    if k > 0:
+        idx[:OVERLAP] = prev[KEYFRAMES]
+    return idx
+
+
+class DepthStream:
+    """``model.stream_video_depth(...)``: whole-video inference, incrementally.  ``push`` takes the frames as they arrive and returns the depth
+    of the frames that became final, ``close`` the rest; for any chunking the concatenation of all they return equals
+    ``model.infer_video_depth(all_frames, stitch="device")`` bit for bit -- the same kernels in the same order.
+
+    Schedule (host arithmetic only: ``stream_trigger``, ``stream_final``): window k runs at the first push that brings the count to
+    22 k + 32; once it is stitched, frames < 24 + 22 k are final.  A chunk that crosses a trigger is taken in pieces, so the ring never holds
+    a frame newer than the trigger of the window about to run.  ``close`` runs the windows that are left (at least one), with the sources of
+    ``window_sources(n)`` -- the padding with the last frame --, and emits up to n.
+
+    Ring: the raw uint8 frames live once in a device ring [STREAM_RING, fh, fw, 3], frame j in slot j % STREAM_RING, uploaded through pinned
+    staging buffers on the copy-in stream.  A window's input is read from its 32 slots on the lane's stream (one edv_ingest_u8 when the frames
+    have the network's size; a gather and the runner's conversion and pre-resize otherwise); key frames are not uploaded a second time.  Window k reads back to frame 22 k - 16 (slot 0: two hops of the key-frame chain), 48 frames in all.
+
+    Stream contract: every push orders itself after what the caller has enqueued on its current stream so far (an event recorded there, for
+    which the copy-in stream, the lanes it uses and the stitch stream wait), as ``HipWindowRunner._run_windows`` does once per run.  A lane
+    waits for the upload of its window's last frame.  Hazard: frame j overwrites frame j - 64, so uploads of frames >= 22 k + 48 race window
+    k's read of the ring: an event is recorded after every window's read, and the copy-in stream waits for it before it uploads any frame after that
+    window's trigger.  The stitch stream takes the windows in window order, whichever lanes they ran on.  Lanes are the model's cached
+    ``_video_flight`` (shared with ``infer_video_depth``); a lora_type="dash" model runs one window at a time on lane 0.  Stitch state, ring
+    and counters belong to this object: two streams of one model may be pushed alternately.
+
+    ``push(chunk, wait=True)`` returns every frame the windows enqueued so far make final and blocks until they are there; ``wait=False``
+    never blocks and returns the finished prefix only.  ``output="host"``: numpy arrays the caller owns; ``"device"``: float32 tensors on the
+    GPU, complete when returned.  Device memory does not grow with the length of the stream.
+
+    ``backend``: the object that touches the GPU (default ``_HipStreamBackend``); tests pass a stub with ``begin_push()``,
+    ``upload(first, frames)``, ``window(k, source, upto)``, ``collect(wait) -> [r, fh, fw]`` and ``release()``."""
+
+    def __init__(self, model, frame_shape: Tuple[int, int], device="cuda", output: str = "host", backend=None):
+        if output not in ("host", "device"):
+            raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+        fh, fw = (int(v) for v in frame_shape)
+        if fh <= 0 or fw <= 0:
+            raise ValueError(f"frame_shape must be (height, width) > 0, got {frame_shape!r}")
+        self.fh, self.fw, self.output = fh, fw, output
+        if backend is None:
+            dev = torch.device(device)
+            if dev.type != "cuda":
+                raise RuntimeError("stream_video_depth runs on MI355X only (device must be a CUDA/ROCm device)")
+            backend = _HipStreamBackend(model, fh, fw, dev, output)
+        self._backend = backend
+        self.pushed = 0          # frames taken
+        self.emitted = 0         # frames returned
+        self.windows = 0         # windows enqueued
+        self.closed = False
+        self._source: Optional[np.ndarray] = None
+
+    def _window(self, source: np.ndarray, upto: int) -> None:
+        self._backend.window(self.windows, source, upto)
+        self._source = source
+        self.windows += 1
+
+    def _collect(self, wait: bool):
+        got = self._backend.collect(wait)
+        self.emitted += int(got.shape[0])
+        return got
+
+    def push(self, chunk, wait: bool = True):
+        if self.closed:
+            raise RuntimeError("push after close: the stream has emitted its last frames")
+        chunk = np.asarray(chunk)
+        if chunk.dtype != np.uint8:
+            raise ValueError(f"expected uint8 frames, got {chunk.dtype}")
+        if chunk.ndim == 3:
+            chunk = chunk[None]
+        if chunk.ndim != 4 or chunk.shape[0] < 1 or chunk.shape[1:] != (self.fh, self.fw, 3):
+            raise ValueError(f"expected frames [m >= 1, {self.fh}, {self.fw}, 3] or one frame [{self.fh}, {self.fw}, 3], got {chunk.shape}")
+        self._backend.begin_push()
+        pos, m = 0, chunk.shape[0]
+        while pos < m:
+            trigger = stream_trigger(self.windows)       # pushed < trigger here: the window would have run
+            take = min(m - pos, trigger - self.pushed)
+            self._backend.upload(self.pushed, chunk[pos:pos + take])
+            self.pushed += take
+            pos += take
+            if self.pushed == trigger:
+                self._window(stream_next_source(self.windows, self._source), stream_final(self.windows))
+        return self._collect(wait)
+
+    def close(self):
+        """The frames not returned yet (``wait`` or not); afterwards ``pushed == emitted``.  A second close returns an empty array."""
+        if not self.closed and self.pushed:
+            n = self.pushed
+            sources = window_sources(n)
+            assert self.windows < len(sources)           # 22 k + 32 <= n implies 22 (k + 1) < n: an eager window is never the last
+            self._backend.begin_push()
+            for k in range(self.windows, len(sources)):
+                self._window(sources[k], n if k == len(sources) - 1 else min(n, stream_final(k)))
+        self.closed = True
+        got = self._collect(True)
+        self._backend.release()
+        return got
+
+
+class _HipStreamBackend:
+    """What ``DepthStream`` does on the GPU (its docstring states the stream contract).  Allocated once: the ring, two pinned staging buffers
+    of 32 frames (a piece between two triggers is at most that long), the stitch state."""
+
+    def __init__(self, model, fh: int, fw: int, dev: torch.device, output: str):
+        self.model, self.fh, self.fw, self.dev, self.on_device = model, fh, fw, dev, output == "device"
+        ih, iw = model.image_shape
+        self.tw, self.th = lower_bound_size(fw, fh, iw, ih)
+        self.lib = _lib.load()
+        with torch.cuda.device(dev):
+            self.s_in = torch.cuda.Stream(device=dev)
+            self.s_st = torch.cuda.Stream(device=dev)
+            # from the pool of the caller's stream, first written on the streams of this object, which wait for the first push's entry event
+            self.ring = torch.empty((STREAM_RING, fh, fw, 3), dtype=torch.uint8, device=dev)
+            self.stitch = _DeviceStitch(self.lib, dev, fh, fw)
+        self.h_in = [torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.up_done: List[Optional[torch.cuda.Event]] = [None, None]  # H2D out of the staging buffer finished
+        self.n_up = 0
+        self.uploaded: Optional[torch.cuda.Event] = None               # the newest frame is in the ring
+        self.ingested: List[torch.cuda.Event] = []                     # ingests the next upload must wait for
+        self.entry: Optional[torch.cuda.Event] = None
+        self.blocks: List[Tuple[torch.Tensor, torch.cuda.Event]] = []  # final frames on their way, in order
+
+    def begin_push(self) -> None:
+        self.entry = torch.cuda.Event()
+        self.entry.record(torch.cuda.current_stream(self.dev))
+        self.s_in.wait_event(self.entry)
+        self.s_st.wait_event(self.entry)
+
+    def upload(self, first: int, frames: np.ndarray) -> None:
+        m = frames.shape[0]
+        b = self.n_up % 2
+        self.n_up += 1
+        if self.up_done[b] is not None:
+            self.up_done[b].synchronize()                # the staging buffer is about to be rewritten
+        stage = self.h_in[b][:m]
+        np.copyto(stage.numpy(), frames)
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.s_in):
+            for ev in self.ingested:                     # the windows whose ring slots these frames may overwrite have read them
+                self.s_in.wait_event(ev)
+            self.ingested = []
+            slot = first % STREAM_RING
+            head = min(m, STREAM_RING - slot)
+            self.ring[slot:slot + head].copy_(stage[:head], non_blocking=True)
+            if head < m:                                 # the piece wraps round the ring
+                self.ring[:m - head].copy_(stage[head:], non_blocking=True)
+            self.up_done[b] = self.uploaded = torch.cuda.Event()
+            self.uploaded.record(self.s_in)
+
+    def window(self, k: int, source: np.ndarray, upto: int) -> None:
+        lib, dev, fh, fw = self.lib, self.dev, self.fh, self.fw
+        with torch.cuda.device(dev), torch.no_grad():
+            dash, _, flight = _video_lanes(self.model, dev)
+            if dash:
+                # lane 0's engine context is single-user: every stream of this model queues its windows on one HIP stream kept with the model
+                stream = getattr(self.model, "_video_dash_stream", None)
+                if stream is None or stream.device != dev:
+                    stream = self.model._video_dash_stream = torch.cuda.Stream(device=dev)
+                lane = 0
+            else:
+                stream, lane = flight.next_lane(INFER_LEN)
+            stream.wait_event(self.entry)                # the first forward on a lane folds and packs the weights on the lane's stream
+            stream.wait_event(self.uploaded)
+            slots = [int(j) % STREAM_RING for j in source]
+            with torch.cuda.stream(stream):
+                st = C.c_void_p(stream.cuda_stream)
+                if (self.th, self.tw) == (fh, fw):
+                    # one kernel over the 32 ring slots, bit-identical to the runner's conversion (tests/test_ingest_gpu.py: all 256 bytes)
+                    cur = torch.empty((INFER_LEN, 3, fh, fw), device=dev, dtype=torch.float32)
+                    _lib.check(lib.edv_ingest_u8(self.ring.data_ptr(), STREAM_RING, (C.c_int32 * INFER_LEN)(*slots), INFER_LEN, cur.data_ptr(), fh, fw, fh, fw, st),
+                               "edv_ingest_u8")
+                else:
+                    # frames that need the pre-resize take the runner's own two steps on a per-window gather of the ring, so that the stream
+                    # equals infer_video_depth bit for bit at every size (DESIGN.md "Streaming": why the fused resize is not used here yet)
+                    clip = torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8, device=dev)
+                    i = 0
+                    while i < INFER_LEN:                 # runs of consecutive slots: the 10 key frames one by one, then 22 frames in one or two copies
+                        r = 1
+                        while i + r < INFER_LEN and slots[i + r] == slots[i] + r:
+                            r += 1
+                        clip[i:i + r].copy_(self.ring[slots[i]:slots[i] + r], non_blocking=True)
+                        i += r
+                    cur = _pre_resize(lib, clip.permute(0, 3, 1, 2).to(torch.float32).div_(255.0), fh, fw, self.th, self.tw, st)
+                done = torch.cuda.Event()
+                done.record(stream)
+                self.ingested.append(done)
+                disp = self.model(cur.unsqueeze(0), lane=lane)[("disp", 0)]  # [32, 1, ih, iw]
+                ready = torch.cuda.Event()
+                ready.record(stream)
+            count = upto - self.stitch.done
+            # a device block comes from the caller's stream's pool (as run_stitched's result does) and is first written on the stitch stream
+            block = torch.empty((count, fh, fw), dtype=torch.float32, device=dev) if self.on_device else torch.empty((count, fh, fw), dtype=torch.float32, pin_memory=True)
+            with torch.cuda.stream(self.s_st):
+                self.s_st.wait_event(ready)
+                g0 = self.stitch.done
+                self.stitch.window(k, disp, self.s_st)
+                for g, piece in self.stitch.final_pieces(upto):
+                    block[g - g0:g - g0 + piece.shape[0]].copy_(piece, non_blocking=True)
+                copied = torch.cuda.Event()
+                copied.record(self.s_st)
+            self.blocks.append((block, copied))
+
+    def collect(self, wait: bool):
+        got = []
+        while self.blocks:
+            block, copied = self.blocks[0]
+            if wait:
+                copied.synchronize()
+            elif not copied.query():
+                break
+            got.append(block)
+            self.blocks.pop(0)
+        if self.on_device:
+            with torch.cuda.device(self.dev):
+                if not got:
+                    return torch.empty((0, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+                if len(got) == 1:
+                    return got[0]
+                out = torch.cat(got)                     # on the caller's stream, from complete blocks
+                torch.cuda.current_stream(self.dev).synchronize()
+                return out
+        if not got:
+            return np.empty((0, self.fh, self.fw), dtype=np.float32)
+        return np.concatenate([b.numpy() for b in got])  # a copy out of the pinned blocks: the caller owns it
+
+    def release(self) -> None:
+        """After the last collect: nothing is in flight; drop the device buffers."""
+        self.ring = self.stitch = None
+        self.h_in = []

@@ -254,6 +254,17 @@ int edv_bicubic_pos(const float *grid_dev, float *out_dev, int32_t S, int32_t D,
  * borders = cv2.INTER_CUBIC): the frame pre-resize of infer_video_depth (endodav.py:170-181,196). */
 int edv_resize_bicubic(const float *x_dev, float *y_dev, int32_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, void *stream);
 
+/* Frame ingest of streamed video (stream_video_depth): out[i] = frame slots[i] of src, uint8 HWC -> [0,1] fp32 planar
+ * CHW, bicubically resized to OH x OW when (OH, OW) != (H, W).  src_dev [src_frames, H, W, 3] uint8; slots_host: n indices into src (host
+ * memory, copied by value into the launch: no upload, no device allocation; NULL = 0..n-1); out_dev [n, 3, OH, OW] fp32.  1 <= n <= 64.
+ * Bit for bit what the two-step path gives (uint8 -> float32 -> div_(255.0) by torch on the device, which multiplies by the fp32
+ * reciprocal of 255, made contiguous planar, then edv_resize_bicubic).  Never reads outside [src_dev, src_dev + src_frames*H*W*3).  Null pointers, n outside
+ * 1..64, a slot outside [0, src_frames) and sizes beyond edv_resize_bicubic's bound return non-zero and launch nothing.
+ * Added without a version bump: an additive entry point leaves edv_config and every existing signature as they are, so EDV_ABI_VERSION
+ * changes only when one of those does. */
+int edv_ingest_u8(const uint8_t *src_dev, int32_t src_frames, const int32_t *slots_host, int32_t n, float *out_dev, int32_t H, int32_t W, int32_t OH,
+                  int32_t OW, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
