@@ -134,6 +134,10 @@ SIGNATURES = {
     "edv_resize_bicubic": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.c_void_p]),
     # additive entry point (ABI stays 15): uint8 frames -> the network's input; the slots are host memory, NULL = identity
     "edv_ingest_u8": (C.c_int, [_fp, _i32, C.POINTER(_i32), _i32, _fp, _i32, _i32, _i32, _i32, C.c_void_p]),
+    # colour-mapped depth (additive, ABI stays 15): range [n][2] fp32 on the device, LUT [256][3] uint8, out uint8
+    "edv_render_workspace": (C.c_size_t, [_i64]),
+    "edv_render_range": (C.c_int, [_fp, _i64, _i32, _i32, _i32, _i64, _i64, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_render_colorize": (C.c_int, [_fp, _i64, _i32, _i32, _fp, _i32, _f32, _i32, _fp, _fp, _fp, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

@@ -259,6 +259,16 @@ int edv_ingest_u8(const uint8_t *src_dev, int32_t src_frames, const int32_t *slo
     return ingest_u8(src_dev, src_frames, slots_host, n, out_dev, H, W, OH, OW, (hipStream_t)stream);
 }
 
+size_t edv_render_workspace(int64_t n) { return render_workspace(n); }
+int edv_render_range(const float *x_dev, int64_t n, int32_t h, int32_t w, int32_t mode, int64_t rank_lo, int64_t rank_hi, float *range_dev, void *workspace_dev,
+                     size_t workspace_bytes, void *stream) {
+    return render_range(x_dev, n, h, w, mode, rank_lo, rank_hi, range_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+int edv_render_colorize(const float *x_dev, int64_t n, int32_t h, int32_t w, const float *range_dev, int32_t range_stride, float eps, int32_t clip,
+                        const uint8_t *lut_dev, const uint8_t *beside_dev, uint8_t *out_dev, void *stream) {
+    return render_colorize(x_dev, n, h, w, range_dev, range_stride, eps, clip, lut_dev, beside_dev, out_dev, (hipStream_t)stream);
+}
+
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream) {

@@ -130,6 +130,11 @@ int metrics_pred(const float *disp, const float *gt, float *pred, long long n, i
 int metrics_errors(const float *pred, const float *gt, long long n, int h, int w, float cap, double *out, void *ws, size_t ws_bytes, hipStream_t stream);
 int metrics_temporal(const float *pred, const float *gt, long long n, int h, int w, float cap, const double *mats, double *out, float *warp, void *ws,
                      size_t ws_bytes, hipStream_t stream);
+// colour-mapped depth on the device (render.hip): x [n, h, w] fp32 -> range [n][2] = (lo, hi) per frame -> uint8 [n, h, w or 2w, 3]
+size_t render_workspace(long long n);  // bytes
+int render_range(const float *x, long long n, int h, int w, int mode, long long rank_lo, long long rank_hi, float *range, void *ws, size_t ws_bytes, hipStream_t stream);
+int render_colorize(const float *x, long long n, int h, int w, const float *range, int range_stride, float eps, int clip, const uint8_t *lut, const uint8_t *beside,
+                    uint8_t *out, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -811,7 +811,7 @@ class endodav(nn.Module):
         return int(_lib.load().edv_device_bytes(C.c_void_p(nat.handle))) if nat else 0
 
     # -------------------------------------------------------------------------------------
-    def infer_video_depth(self, frames, input_size=518, device="cuda", shard_windows=False, stitch="host", output="host"):
+    def infer_video_depth(self, frames, input_size=518, device="cuda", shard_windows=False, stitch="host", output="host", render=None):
         """Sliding-window inference over a whole video (endodav.py:162-254).
 
         ``frames``: uint8 [N, H, W, 3].  Returns float32 [N, H, W].  Windows of 32 frames, step 22; the
@@ -823,16 +823,18 @@ class endodav(nn.Module):
         float32 on the host; the result agrees with the default's to about 1e-6 of its scale and is not bit-identical to it.
         ``output="device"`` (needs ``stitch="device"``): the same result as a float32 ``torch.Tensor`` [N, H, W] on the GPU, never copied to the
         host; all work is drained before the call returns (``video.infer_video_depth``).
+        ``render`` (a ``render.Render``; needs ``stitch="device"``): the colour-mapped video, uint8 [N, H, W, 3], coloured on the GPU.
         """
         from .video import infer_video_depth as _impl
 
-        return _impl(self, frames, input_size=input_size, device=device, shard_windows=shard_windows, stitch=stitch, output=output)
+        return _impl(self, frames, input_size=input_size, device=device, shard_windows=shard_windows, stitch=stitch, output=output, render=render)
 
-    def stream_video_depth(self, frame_shape, device="cuda", output="host"):
+    def stream_video_depth(self, frame_shape, device="cuda", output="host", render=None):
         """``infer_video_depth(stitch="device")`` for a live feed (not in the reference): returns a ``video.DepthStream`` whose
         ``push(chunk)`` takes uint8 frames [m, H, W, 3] as they arrive and returns the float32 depth [r, H, W] of the frames that became
         final, and whose ``close()`` returns the rest.  Whatever the chunking, the concatenation equals the offline result bit for bit.
-        Depth lags the newest frame by at most 29 frames between windows (the reference's 32-frame windows with an 8-frame cross-fade)."""
+        Depth lags the newest frame by at most 29 frames between windows (the reference's 32-frame windows with an 8-frame cross-fade).
+        ``render`` (a ``render.Render``, any norm but "video"): ``push`` / ``close`` return colour-mapped frames, uint8 [r, H, W, 3]."""
         from .video import DepthStream
 
-        return DepthStream(self, frame_shape, device=device, output=output)
+        return DepthStream(self, frame_shape, device=device, output=output, render=render)

@@ -318,7 +318,7 @@ class HipWindowRunner:
             drain(k % nbuf)
         return results
 
-    def run_stitched(self, sources: Sequence[np.ndarray], n_keep: int, output: str = "host"):
+    def run_stitched(self, sources: Sequence[np.ndarray], n_keep: int, output: str = "host", render=None):
         """``stitch="device"``: all windows of the video (``window_sources``) -> the stitched result [n_keep, fh, fw], float32, in pinned host memory
         (``output="host"``) or, by the same kernels and with the same bits, as a tensor on the device (``output="device"``: the final frames are
         copied device-to-device instead of to the pinned buffer).  Either way all work is drained before the call returns.
@@ -330,14 +330,25 @@ class HipWindowRunner:
         frame-size maps of a window exist nowhere; two frame-size buffers [32, fh, fw] alternate between the windows (the tail is the end of the
         previous window's buffer), whatever the length of the video.  Padding frames beyond ``n_keep`` are computed and never copied.
         A window's disparity is a tensor of the lane's allocator pool: ``record_stream`` keeps its memory from being handed out again before
-        the stitch stream has read it."""
+        the stitch stream has read it.
+
+        ``render`` (a ``render.Render``): the result is the coloured video, uint8 [n_keep, fh, fw, 3].  For "frame", "fixed" and "quantile" the
+        stitch stream colours every block of final frames where it would have copied it (``render.DeviceRenderer``) and copies the uint8 block
+        into the result: no fp32 video exists anywhere and 3 bytes a pixel leave the device instead of 4.  "video" needs the range of the
+        whole video first: the fp32 video is built on the device as for ``output="device"``, then one range pass, then the colouring."""
         lib = _lib.load()
         dev, fh, fw = self.dev, self.fh, self.fw
         step = INFER_LEN - OVERLAP
         last = len(sources) - 1
         on_device = output == "device"
+        if render is not None and render.norm == "video":
+            from . import render as render_mod
+
+            with torch.cuda.device(dev):
+                return render_mod.colorize(self.run_stitched(sources, n_keep, output="device"), render, output=output)
+        shape, dtype = ((n_keep, fh, fw), torch.float32) if render is None else ((n_keep, fh, fw, 3), torch.uint8)
         if last < 0:
-            return torch.empty((0, fh, fw), dtype=torch.float32, device=dev) if on_device else np.empty((0, fh, fw), dtype=np.float32)
+            return torch.empty((0,) + shape[1:], dtype=dtype, device=dev) if on_device else torch.empty((0,) + shape[1:], dtype=dtype).numpy()
         s_st = torch.cuda.Stream(device=dev)
         state: dict = {"done": 0}
 
@@ -345,7 +356,11 @@ class HipWindowRunner:
             s_st.wait_event(entry)
             state["stitch"] = _DeviceStitch(lib, dev, fh, fw, min(2, len(sources)))
             # the device result comes from the caller's stream's pool and is first written on the stitch stream, which has waited for `entry`
-            state["out"] = torch.empty((n_keep, fh, fw), dtype=torch.float32, device=dev) if on_device else torch.empty((n_keep, fh, fw), dtype=torch.float32, pin_memory=True)
+            state["out"] = torch.empty(shape, dtype=dtype, device=dev) if on_device else torch.empty(shape, dtype=dtype, pin_memory=True)
+            if render is not None:
+                from .render import DeviceRenderer
+
+                state["render"] = DeviceRenderer(render, dev, fh, fw, staging=not on_device)
 
         def after_forward(k: int, slot: int, stream: torch.cuda.Stream, disp: torch.Tensor) -> None:
             stitch, out = state["stitch"], state["out"]
@@ -356,7 +371,10 @@ class HipWindowRunner:
                 stitch.window(k, disp, s_st)
                 upto = n_keep if k == last else min(n_keep, INFER_LEN + step * k - INTERP_LEN)
                 for g, piece in stitch.final_pieces(upto):
-                    out[g:g + piece.shape[0]].copy_(piece, non_blocking=True)
+                    if render is None:
+                        out[g:g + piece.shape[0]].copy_(piece, non_blocking=True)
+                    else:
+                        state["render"].color_into(piece, out[g:g + piece.shape[0]])
                 state["done"] = stitch.done
 
         self._run_windows(sources, begin, lambda k, slot: None, after_forward)
@@ -378,7 +396,8 @@ class HipWindowRunner:
 
 
 # ---------------------------------------------------------------------------------------------
-def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None, shard_windows=False, rank=None, world=None, stitch="host", output="host"):
+def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None, shard_windows=False, rank=None, world=None, stitch="host", output="host",
+                      render=None):
     """endodav.infer_video_depth (endodav.py:162-254).  By default every window of the video runs on the calling rank, whatever process group
     exists: that is what ``evaluate.evaluate_video`` needs, where each rank already holds a DIFFERENT clip (sharding the windows of those clips
     over the same ranks would pair up collectives of different clips -- ADVICE round 2).
@@ -399,9 +418,13 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
     same bits, the final frames copied device-to-device instead of to the host (what ``evaluate.evaluate_video(metrics="device")`` consumes).
     All work is drained before the call returns, as for the host result: the tensor can be used on any stream at once.
 
+    ``render``: None (default) or a ``render.Render`` (needs ``stitch="device"``, does not combine with ``shard_windows=True``): the result is
+    the colour-mapped video, uint8 [n, fh, fw, 3], in pinned host memory or (``output="device"``) on the GPU, coloured on the stitch stream
+    (``HipWindowRunner.run_stitched``); it equals ``render.colorize`` of the fp32 result byte for byte.
+
     ``runner``: anything with ``run(sources) -> [np.ndarray [32, H, W]]`` (default ``HipWindowRunner``; the gloo tests pass a stub);
-    ``stitch="device"`` needs its ``run_stitched(sources, n) -> np.ndarray [n, H, W]`` as well, and ``output="device"`` that it takes
-    ``output="device"``."""
+    ``stitch="device"`` needs its ``run_stitched(sources, n) -> np.ndarray [n, H, W]`` as well, ``output="device"`` that it takes
+    ``output="device"``, and ``render`` that it takes ``render=``."""
     from . import parallel
 
     if stitch not in ("host", "device"):
@@ -412,6 +435,13 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
         raise ValueError("output='device' needs stitch='device' and does not combine with shard_windows=True: only the device stitch leaves the video on the GPU")
     if stitch == "device" and shard_windows:
         raise ValueError("stitch='device' does not combine with shard_windows=True: sharded windows are gathered and stitched on the host of rank 0")
+    if render is not None:
+        from .render import Render
+
+        if not isinstance(render, Render):
+            raise ValueError(f"render must be None or a render.Render, got {type(render).__name__}")
+        if stitch != "device" or shard_windows:
+            raise ValueError("render needs stitch='device' and does not combine with shard_windows=True: the frames are coloured where the device stitch finishes them")
     frames = np.asarray(frames)
     if frames.ndim != 4 or frames.shape[-1] != 3:
         raise ValueError(f"expected frames [N, H, W, 3], got {frames.shape}")
@@ -423,7 +453,8 @@ def infer_video_depth(model, frames, input_size=518, device="cuda", runner=None,
         runner = HipWindowRunner(model, np.ascontiguousarray(frames), dev)
     sources = window_sources(n)
     if stitch == "device":
-        return runner.run_stitched(sources, n, output="device") if output == "device" else runner.run_stitched(sources, n)
+        kw = {} if render is None else {"render": render}  # a keyword reaches the runner only when it is not the default
+        return runner.run_stitched(sources, n, output="device", **kw) if output == "device" else runner.run_stitched(sources, n, **kw)
     if not shard_windows:
         return stitch_windows(runner.run(sources), n)
     if rank is None or world is None:
@@ -487,12 +518,26 @@ class DepthStream:
     never blocks and returns the finished prefix only.  ``output="host"``: numpy arrays the caller owns; ``"device"``: float32 tensors on the
     GPU, complete when returned.  Device memory does not grow with the length of the stream.
 
+    ``render`` (a ``render.Render`` with norm "frame", "fixed" or "quantile"; "video" needs the whole video and raises): ``push`` and ``close``
+    return the colour-mapped frames, uint8 [r, fh, fw, 3], coloured on the stitch stream where the fp32 frames would have been copied; the
+    concatenation equals ``infer_video_depth(..., stitch="device", render=render)``.  The table, the range workspace and the staging buffer are
+    allocated once with the ring.  Side by side with the input frames is ``render.colorize(frames=...)`` only: the ring may have dropped a
+    frame by the time its depth is final.
+
     ``backend``: the object that touches the GPU (default ``_HipStreamBackend``); tests pass a stub with ``begin_push()``,
     ``upload(first, frames)``, ``window(k, source, upto)``, ``collect(wait) -> [r, fh, fw]`` and ``release()``."""
 
-    def __init__(self, model, frame_shape: Tuple[int, int], device="cuda", output: str = "host", backend=None):
+    def __init__(self, model, frame_shape: Tuple[int, int], device="cuda", output: str = "host", backend=None, render=None):
         if output not in ("host", "device"):
             raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+        if render is not None:
+            from .render import Render
+
+            if not isinstance(render, Render):
+                raise ValueError(f"render must be None or a render.Render, got {type(render).__name__}")
+            if render.norm == "video":
+                raise ValueError("render.norm='video' needs the range of the whole video, which a stream never sees: use 'frame', 'fixed' or 'quantile'")
+        self.render = render
         fh, fw = (int(v) for v in frame_shape)
         if fh <= 0 or fw <= 0:
             raise ValueError(f"frame_shape must be (height, width) > 0, got {frame_shape!r}")
@@ -501,7 +546,7 @@ class DepthStream:
             dev = torch.device(device)
             if dev.type != "cuda":
                 raise RuntimeError("stream_video_depth runs on MI355X only (device must be a CUDA/ROCm device)")
-            backend = _HipStreamBackend(model, fh, fw, dev, output)
+            backend = _HipStreamBackend(model, fh, fw, dev, output, render)
         self._backend = backend
         self.pushed = 0          # frames taken
         self.emitted = 0         # frames returned
@@ -560,8 +605,9 @@ class _HipStreamBackend:
     """What ``DepthStream`` does on the GPU (its docstring states the stream contract).  Allocated once: the ring, two pinned staging buffers
     of 32 frames (a piece between two triggers is at most that long), the stitch state."""
 
-    def __init__(self, model, fh: int, fw: int, dev: torch.device, output: str):
+    def __init__(self, model, fh: int, fw: int, dev: torch.device, output: str, render=None):
         self.model, self.fh, self.fw, self.dev, self.on_device = model, fh, fw, dev, output == "device"
+        self.shape, self.dtype = ((fh, fw), torch.float32) if render is None else ((fh, fw, 3), torch.uint8)
         ih, iw = model.image_shape
         self.tw, self.th = lower_bound_size(fw, fh, iw, ih)
         self.lib = _lib.load()
@@ -571,6 +617,11 @@ class _HipStreamBackend:
             # from the pool of the caller's stream, first written on the streams of this object, which wait for the first push's entry event
             self.ring = torch.empty((STREAM_RING, fh, fw, 3), dtype=torch.uint8, device=dev)
             self.stitch = _DeviceStitch(self.lib, dev, fh, fw)
+            self.render = None
+            if render is not None:
+                from .render import DeviceRenderer
+
+                self.render = DeviceRenderer(render, dev, fh, fw, staging=not self.on_device)
         self.h_in = [torch.empty((INFER_LEN, fh, fw, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.up_done: List[Optional[torch.cuda.Event]] = [None, None]  # H2D out of the staging buffer finished
         self.n_up = 0
@@ -647,13 +698,16 @@ class _HipStreamBackend:
                 ready.record(stream)
             count = upto - self.stitch.done
             # a device block comes from the caller's stream's pool (as run_stitched's result does) and is first written on the stitch stream
-            block = torch.empty((count, fh, fw), dtype=torch.float32, device=dev) if self.on_device else torch.empty((count, fh, fw), dtype=torch.float32, pin_memory=True)
+            block = torch.empty((count,) + self.shape, dtype=self.dtype, device=dev) if self.on_device else torch.empty((count,) + self.shape, dtype=self.dtype, pin_memory=True)
             with torch.cuda.stream(self.s_st):
                 self.s_st.wait_event(ready)
                 g0 = self.stitch.done
                 self.stitch.window(k, disp, self.s_st)
                 for g, piece in self.stitch.final_pieces(upto):
-                    block[g - g0:g - g0 + piece.shape[0]].copy_(piece, non_blocking=True)
+                    if self.render is None:
+                        block[g - g0:g - g0 + piece.shape[0]].copy_(piece, non_blocking=True)
+                    else:
+                        self.render.color_into(piece, block[g - g0:g - g0 + piece.shape[0]])
                 copied = torch.cuda.Event()
                 copied.record(self.s_st)
             self.blocks.append((block, copied))
@@ -671,17 +725,17 @@ class _HipStreamBackend:
         if self.on_device:
             with torch.cuda.device(self.dev):
                 if not got:
-                    return torch.empty((0, self.fh, self.fw), dtype=torch.float32, device=self.dev)
+                    return torch.empty((0,) + self.shape, dtype=self.dtype, device=self.dev)
                 if len(got) == 1:
                     return got[0]
                 out = torch.cat(got)                     # on the caller's stream, from complete blocks
                 torch.cuda.current_stream(self.dev).synchronize()
                 return out
         if not got:
-            return np.empty((0, self.fh, self.fw), dtype=np.float32)
+            return torch.empty((0,) + self.shape, dtype=self.dtype).numpy()
         return np.concatenate([b.numpy() for b in got])  # a copy out of the pinned blocks: the caller owns it
 
     def release(self) -> None:
         """After the last collect: nothing is in flight; drop the device buffers."""
-        self.ring = self.stitch = None
+        self.ring = self.stitch = self.render = None
         self.h_in = []

@@ -265,6 +265,37 @@ int edv_resize_bicubic(const float *x_dev, float *y_dev, int32_t planes, int32_t
 int edv_ingest_u8(const uint8_t *src_dev, int32_t src_frames, const int32_t *slots_host, int32_t n, float *out_dev, int32_t H, int32_t W, int32_t OH,
                   int32_t OW, void *stream);
 
+/* ---- colour-mapped depth on the device (render.colorize, infer_video_depth(render=...), stream_video_depth(render=...); the numpy of
+ * utils/eval_utils.py:284-295 save_video, evaluate_depth_video.py:32-36 render_depth and test_simple.py:156-167) ----
+ * Additive entry points: the ABI version stays as it is (the rule stated at edv_ingest_u8).  A clip is x_dev [n, h, w] fp32, h*w < 2^31.
+ * Every operation is fp32, not contracted, in the order written here: the results are numpy's bits.  Inputs are finite: NaN is unsupported.
+ * edv_render_range writes range_dev [n][2] = (lo, hi) per frame.
+ *   mode 0 "frame":    the frame's minimum and maximum.
+ *   mode 1 "video":    the minimum and maximum of all n*h*w elements (a 64-bit count), written to every one of the n rows.
+ *   mode 2 "quantile": per frame the order statistics of rank rank_lo and rank_hi (0 <= rank_lo <= rank_hi < h*w, the same for every frame):
+ *                      np.sort(frame.ravel())[rank].  Exact radix select on the order-preserving integer image of the float bits, four 8-bit
+ *                      histogram passes, both statistics followed at once (one histogram until their prefixes part), LDS counters flushed
+ *                      with 64-bit integer atomics.  Batched: one launch per pass for all frames of a chunk (the frame on blockIdx.y, a
+ *                      select state per frame in the workspace): eight launches for up to 64 frames, whatever their number.
+ *   All three compare those integer keys, so -0.0 orders below +0.0 (numpy leaves the choice between them open; no colour depends on it).
+ *   rank_lo and rank_hi are ignored by modes 0 and 1.  Integer atomics only: the same input gives the same bits on every call.
+ * edv_render_workspace(n): bytes edv_render_range needs for n frames, 16-byte aligned memory; frames go in chunks of 64, so it stops growing there.
+ * edv_render_colorize: out[f, y, x, :] = lut[idx] with, per pixel of frame f and (lo, hi) = range_dev[f * range_stride + {0, 1}]
+ *   (range_stride 2: a pair per frame; 0: one pair for all frames),
+ *     den = (hi - lo) + eps;  t = (x - lo) / den  (IEEE division);  if clip: t = min(max(t, 0), 1);
+ *     idx = den == 0 ? 0 : (uint8) trunc(t * 255.0f), clamped to 0..255.
+ *   lut_dev [256][3] uint8; out_dev [n, h, w, 3] uint8 in the table's channel order.  With beside_dev [n, h, w, 3] uint8 (may be NULL)
+ *   out_dev is [n, h, 2w, 3]: each row the row of beside_dev followed by the colour row (save_video's np.concatenate(..., axis=1)).
+ *   When w % 4 == 0, x_dev is 16-byte and out_dev / beside_dev are 4-byte aligned, a thread reads four pixels in one 16-byte load and writes
+ *   their 12 bytes as three whole dwords; one byte per store otherwise.  Never writes outside out_dev's n*h*w*3 (or n*h*2w*3) bytes.
+ * Null pointers, n < 1, h or w < 1, h*w >= 2^31, an unknown mode or stride, rank_lo > rank_hi, a rank >= h*w, a workspace that is missing,
+ * short or not 16-byte aligned return non-zero and launch nothing. */
+size_t edv_render_workspace(int64_t n);
+int edv_render_range(const float *x_dev, int64_t n, int32_t h, int32_t w, int32_t mode, int64_t rank_lo, int64_t rank_hi, float *range_dev,
+                     void *workspace_dev, size_t workspace_bytes, void *stream);
+int edv_render_colorize(const float *x_dev, int64_t n, int32_t h, int32_t w, const float *range_dev, int32_t range_stride, float eps, int32_t clip,
+                        const uint8_t *lut_dev, const uint8_t *beside_dev, uint8_t *out_dev, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
