@@ -8,6 +8,29 @@
 // 1.9-2.1e-8 of sum |a w| against 2.1-2.4e-8 for the v_mfma_f32_32x32x2_f32 kernels, the same maximum.  Six v_mfma_f32_32x32x16_bf16 take 192
 // matrix-pipe cycles per 16 k where eight v_mfma_f32_32x32x2_f32 take 512; the fp32 pipe's 157 TFLOP/s stops being the ceiling.
 //
+// Input domain of that claim (tests/test_x6_edges_gpu.py, tests/test_x6_inputs_cpu.py; attn_x6_kernel of attn_spatial.hip shares the construction and
+// the domain): finite operands with 2^-100 <= |x| <= 2^100, or exactly 0.
+//   * Inside it the claim holds on operands the uniform test never sees.  Error against fp64 relative to sum |a w| in u = 2^-24, bf16 x 6 against the
+//     fp32-MFMA kernel on the same operands, as rms6/rms32 and max6/max32, at 600 x 512 x 768 plain | stream-K | 257 x 200 x 64, MI355X:
+//       three A channels x 1e3          0.64 0.60 | 0.65 0.45 | 0.69 0.85     (largest error 22 u against the fp32 kernel's 37 u)
+//       ... and two W channels x 1e3    0.63 0.72 | 0.64 0.68 | 0.71 0.79     (28 u against 39 u)
+//       lognormal A (sigma 2)           0.75 0.63 | 0.77 0.57 | 0.79 0.83     (17 u against 27 u)
+//       cancelling halves of k          0.83 0.95 | 0.66 0.99 | 0.84 0.75     (2.7 u against 2.9 u)
+//       A 2^100, A 2^-100, W 2^-100     0.84 0.81 | 0.81 0.94 | 0.76 0.72     (the same bits at all three: 4.0 u against 4.9 u)
+//     So "no worse than the fp32 pipe, in rms and in the maximum" stands as stated; "within a few unit roundoffs" does NOT carry over to outlier
+//     channels and heavy tails -- for either kernel: there the error of correct fp32 accumulation is tens of u of sum |a w| (bounded by K u), and
+//     a gate normalised by the largest output hides it.  Scaling an operand by a power of two inside the domain scales the result bit for bit.
+//   * Below it the third term, then the second, go subnormal and lose bits; the leading term keeps the result finite and within 2^-8 of sum |a w|.
+//     A 2^s, uniform |a| < 2, |w| < 0.05, 600 x 512 x 768 (rms error in u; the fp32 kernel stays at 0.20 throughout, 0.25 at -124):
+//       s = 0 and -100 .. -108: 0.17     -112: 0.20     -116: 1.55     -120: 24.7     -124: 395       (ratio to fp32: 0.81, 1.0, 7.6, 121, 1553)
+//     These are the figures of a CPU emulation that KEEPS bf16 subnormals (flushing them would give 1.0 u at -108 and 246 u at -116): on gfx950 both
+//     the fp32 -> bf16 conversion and the bf16 MFMA's inputs keep subnormals, so the range ends near 2^-110, not 2^-101.
+//   * Above it, and for non-finite operands: +-Inf splits into p0 = +-Inf, p1 = Inf - Inf = NaN, and any finite |x| >= 3.3962e38 rounds to a bf16 Inf
+//     and splits into +Inf, -Inf, NaN.  Either way the products hold NaN where the fp32 kernels give +-Inf (a NaN operand gives NaN in both).  That
+//     NaN stays where the operand is: a non-finite entry of A row m makes output row m non-finite, one of W row n output column n, and every
+//     other row / column keeps its bits -- row M - 1 and weight row N - 1, which the clamped loads of a ragged tile duplicate into padding rows that
+//     are never stored, included; whole tiles and stream-K pieces alike.  Nothing in the k loop guards against it: that would be VALU work there.
+//
 // W (static) is split once into three bf16 planes [3][N][K] (edv_prepare / edv_refresh_lora) and streams to LDS by LDS-DMA.  A (activations, fp32 in
 // HBM, written by fp32 producers) is split on the way: the staging threads load 16-byte pieces to registers, split them (v_cvt_pk_bf16_f32 + two
 // subtractions per plane) and write the three planes to LDS.  That is vector-ALU work in the k loop, which gemm_dma.hip avoids at all cost -- but beside the

@@ -159,7 +159,14 @@ int edv_gemm(const float *A_dev, const float *W_dev, float *C_dev, int64_t M, in
  * (it starts with per-tile arrival counters, which every launch leaves at zero).  workspace_dev = NULL: one workgroup per tile. */
 size_t edv_gemm_workspace(void);
 /* The same GEMM with its products on the bf16 matrix pipe (EDV_PRODUCTS_BF16X6): split the weight once into planes_dev
- * (edv_gemm_x6_planes_bytes(N, K) bytes), then call edv_gemm_x6 with the planes in place of W.  K % 16 == 0, N >= 64. */
+ * (edv_gemm_x6_planes_bytes(N, K) bytes), then call edv_gemm_x6 with the planes in place of W.  K % 16 == 0, N >= 64.
+ * Input domain (A and W alike; csrc/gemm_x6.hip has the measurements): the accuracy claim -- error no worse than edv_gemm's on the same
+ * operands -- holds for finite values with 2^-100 <= |x| <= 2^100, or exactly 0; scaling an operand by a power of two inside that range scales
+ * the result bit for bit.  Below it the result degrades gracefully (the lower bf16 terms go subnormal: equal to edv_gemm down to |x| ~ 2^-110,
+ * 8 x its rms error at 2^-116, 120 x at 2^-120; always finite and within 2^-8 of sum |a w|).  A non-finite value, or a finite |x| >= 3.3962e38
+ * (it rounds to a bf16 Inf), yields NaN where edv_gemm yields +-Inf / NaN: edv_gemm_x6_split writes Inf / NaN planes for such a weight row and
+ * edv_gemm_x6 splits A the same way.  That NaN is confined: an entry of A row m reaches output row m only, one of W row n output column n
+ * only; every other output element keeps the bits it has without it. */
 size_t edv_gemm_x6_planes_bytes(int32_t N, int32_t K);
 int edv_gemm_x6_split(const float *W_dev, void *planes_dev, int32_t N, int32_t K, void *stream);
 int edv_gemm_x6(const float *A_dev, const void *planes_dev, float *C_dev, int64_t M, int32_t N, int32_t K, const float *bias_dev, int32_t act,
@@ -198,7 +205,12 @@ int edv_attn_spatial(const float *qkv_dev, float *out_dev, int32_t F, int32_t N,
  * backward needs.  edv_attn_spatial_bwd: dqkv [F*N, 3*heads*64] (like qkv) from qkv, out, dout [F*N, heads*64] and lse;
  * delta_dev is [F, heads, N] floats of scratch. */
 /* The same attention with both products on the bf16 matrix pipe (EDV_PRODUCTS_BF16X6: three-term bf16 splits of q, k, v and of the probabilities,
- * six bf16 MFMAs per 16 k, fp32 accumulate and fp32 softmax; sequences longer than 128, shorter ones run the fp32 kernel).  Its own workspace size. */
+ * six bf16 MFMAs per 16 k, fp32 accumulate and fp32 softmax; sequences longer than 128, shorter ones run the fp32 kernel).  Its own workspace size.
+ * Input domain as for edv_gemm_x6: finite q, k, v with 2^-100 <= |x| <= 2^100 or exactly 0 (v scaled by a power of two scales the output bit for
+ * bit; q scaled by 2^s and k by 2^-s leave it unchanged bit for bit).  A non-finite entry, or a finite |x| >= 3.3962e38, yields NaN where
+ * edv_attn_spatial may yield +-Inf, and stays confined as there: one in a q row of head h makes that output row of head h non-finite and nothing
+ * else; one in a k or v row of (frame f, head h) may make the output of that (f, h) block non-finite and leaves every other (frame, head) block
+ * bit for bit as it is without it. */
 size_t edv_attn_spatial_x6_workspace(int32_t F, int32_t N, int32_t heads);
 int edv_attn_spatial_x6(const float *qkv_dev, float *out_dev, int32_t F, int32_t N, int32_t heads, float *workspace_dev, size_t workspace_bytes,
                         void *stream);
