@@ -4,6 +4,10 @@
 //   GroupNorm(32, eps 1e-6) on the motion-module input: motion_module.py:84,110
 // One wave per row; the row lives in registers (float4 per lane), mean and the centred second
 // moment are reduced with wavefront shuffles (two-pass in registers: no E[x^2]-E[x]^2 cancellation).
+// GroupNorm sums thousands of values per slab, so the fp32 mean of pass 1 is a few ulps off (delta); left alone, pass 2 returns var + delta^2,
+// which at |mean| / sigma = 6e4 put 2e-5 into rstd.  Pass 2 therefore also sums the centred values d (sum d = n delta) and every statistics
+// kernel applies the corrected two-pass form  M2 = sum d^2 - (sum d)^2 / n,  mean += sum d / n  (Chan, Golub & LeVeque 1983): rstd then
+// holds to fp32 rounding whatever the offset.  On a constant slab every d is 0 and both corrections vanish: mean and y stay exact.
 #include <cstdlib>
 
 #include "ops.hpp"
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
 // GroupNorm statistics: one workgroup per (frame, group); x is channels-last [F, P, C].
 // Pass 1 mean, pass 2 centred second moment (the slab is re-read from L2).
 __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float *__restrict__ x, float *__restrict__ stats, int P, int C, int groups, float eps) {
-    __shared__ float red[4];
+    __shared__ float red[4], red2[4];
     __shared__ float bc;
     const int f = blockIdx.y, g = blockIdx.x, cg = C / groups;
     const float *xf = x + (long long)f * P * C + g * cg;
@@ -107,31 +111,37 @@ __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const float *__res
     if (threadIdx.x == 0) bc = (red[0] + red[1] + red[2] + red[3]) / (float)n;
     __syncthreads();
     const float mean = bc;
-    float q = 0.f;
+    float q = 0.f, sd = 0.f;
 #pragma unroll 8
     for (int i = threadIdx.x; i < n; i += 256) {
         const int p = i / cg, c = i - p * cg;
         const float d = xf[(long long)p * C + c] - mean;
         q += d * d;
+        sd += d;
     }
     q = wave_sum(q);
+    sd = wave_sum(sd);
     __syncthreads();
-    if (lane == 0) red[wv] = q;
+    if (lane == 0) {
+        red[wv] = q;
+        red2[wv] = sd;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float var = (red[0] + red[1] + red[2] + red[3]) / (float)n;
-        stats[((long long)f * groups + g) * 2 + 0] = mean;
+        const float sdt = (red2[0] + red2[1]) + (red2[2] + red2[3]);  // n (true mean - mean): what pass 1's sum lost to rounding
+        const float var = fmaxf((red[0] + red[1] + red[2] + red[3]) - sdt * sdt / (float)n, 0.f) / (float)n;
+        stats[((long long)f * groups + g) * 2 + 0] = mean + sdt / (float)n;
         stats[((long long)f * groups + g) * 2 + 1] = rsqrtf(var + eps);
     }
 }
 
 // Two-stage statistics with coalesced reads (the kernel above reads cg = C / groups floats of every 4C-byte pixel row per workgroup:
 // 15 us at [8, 5476, 64]).  Stage 1: one workgroup per (32-pixel chunk, frame) reads whole rows as float4 and leaves, per channel, the
-// chunk's mean and centred second moment (two passes over the chunk, the second from L2).  Stage 2: one wave per (frame, group) merges
-// the (chunk, channel) pairs with the parallel-variance formula  M2 = sum M2_i + sum n_i (mean_i - mean)^2  -- as accurate as two passes.
+// chunk's mean (as an fp32 value plus a correction) and centred second moment (two passes over the chunk, the second from L2).  Stage 2: one wave
+// per (frame, group) merges the (chunk, channel) triples with the parallel-variance formula  M2 = sum M2_i + sum n_i (mean_i - mean)^2  -- as accurate as two passes.
 constexpr int GN_ROWS = 32;
 __global__ __launch_bounds__(256) void groupnorm_partial_kernel(const float *__restrict__ x, float *__restrict__ part, int P, int C, int nch) {
-    __shared__ f32x4 red[256];
+    __shared__ f32x4 red[256], red2[256];
     __shared__ f32x4 meanq[256];
     const int c4n = C >> 2, rpp = 256 / c4n, tid = threadIdx.x;
     const bool active = tid < rpp * c4n;
@@ -151,20 +161,29 @@ __global__ __launch_bounds__(256) void groupnorm_partial_kernel(const float *__r
     }
     __syncthreads();
     const f32x4 m = meanq[cq];
-    f32x4 q = {0.f, 0.f, 0.f, 0.f};
+    f32x4 q = {0.f, 0.f, 0.f, 0.f}, sd = {0.f, 0.f, 0.f, 0.f};
     if (active)
         for (int p = p0 + r0; p < p1; p += rpp) {
             const f32x4 d = *reinterpret_cast<const f32x4 *>(xf + (long long)p * C) - m;
             q += d * d;
+            sd += d;
         }
     red[tid] = q;
+    red2[tid] = sd;
     __syncthreads();
     if (tid < c4n) {
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < rpp; ++k) t += red[k * c4n + tid];
-        float *o = part + (((long long)f * nch + chunk) * 2) * C + tid * 4;
+        f32x4 t = {0.f, 0.f, 0.f, 0.f}, u = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < rpp; ++k) {
+            t += red[k * c4n + tid];
+            u += red2[k * c4n + tid];
+        }
+        const float rn = 1.0f / (float)(p1 - p0);
+        // corrected two-pass: u = n (true chunk mean - meanq).  The correction travels as a second float: rounded into meanq it would be lost
+        // again to ulp(mean) / 2, and the merge below would take that for spread between the chunks (1e-4 of rstd at |mean| / sigma = 6e4)
+        float *o = part + (((long long)f * nch + chunk) * 3) * C + tid * 4;
         *reinterpret_cast<f32x4 *>(o) = meanq[tid];
-        *reinterpret_cast<f32x4 *>(o + C) = t;
+        *reinterpret_cast<f32x4 *>(o + C) = u * rn;
+        *reinterpret_cast<f32x4 *>(o + 2 * C) = t - u * u * rn;
     }
 }
 
@@ -172,25 +191,28 @@ __global__ __launch_bounds__(64) void groupnorm_finish_kernel(const float *__res
                                                               float eps) {
     const int f = blockIdx.y, g = blockIdx.x, cg = C / groups, lane = threadIdx.x;
     const int items = nch * cg;
-    const float *pf = part + ((long long)f * nch * 2) * C + g * cg;
+    const float *pf = part + ((long long)f * nch * 3) * C + g * cg;  // per chunk: mean | its correction | M2, C floats each
     float sw = 0.f;
     for (int i = lane; i < items; i += 64) {
         const int ch = i / cg, c = i - ch * cg;
         const int n = (ch + 1) * GN_ROWS <= P ? GN_ROWS : P - ch * GN_ROWS;
-        sw += (float)n * pf[(long long)ch * 2 * C + c];
+        sw += (float)n * pf[(long long)ch * 3 * C + c];
     }
     const float mean = wave_sum(sw) / ((float)P * (float)cg);
-    float m2 = 0.f;
+    float m2 = 0.f, sd = 0.f;
     for (int i = lane; i < items; i += 64) {
         const int ch = i / cg, c = i - ch * cg;
         const int n = (ch + 1) * GN_ROWS <= P ? GN_ROWS : P - ch * GN_ROWS;
-        const float d = pf[(long long)ch * 2 * C + c] - mean;
-        m2 += pf[(long long)ch * 2 * C + C + c] + (float)n * d * d;
+        const float d = (pf[(long long)ch * 3 * C + c] - mean) + pf[(long long)ch * 3 * C + C + c];
+        m2 += pf[(long long)ch * 3 * C + 2 * C + c] + (float)n * d * d;
+        sd += (float)n * d;
     }
     m2 = wave_sum(m2);
+    sd = wave_sum(sd);  // N (true mean - mean): the rounding of the weighted sum above
     if (lane == 0) {
-        stats[((long long)f * groups + g) * 2 + 0] = mean;
-        stats[((long long)f * groups + g) * 2 + 1] = rsqrtf(m2 / ((float)P * (float)cg) + eps);
+        const float N = (float)P * (float)cg;
+        stats[((long long)f * groups + g) * 2 + 0] = mean + sd / N;
+        stats[((long long)f * groups + g) * 2 + 1] = rsqrtf(fmaxf(m2 - sd * sd / N, 0.f) / N + eps);
     }
 }
 
@@ -255,7 +277,7 @@ int layernorm(const float *x, RowMap in_map, const float *w, const float *b, flo
     return 0;
 }
 
-size_t groupnorm_workspace(int F, int P, int C) { return (size_t)F * ((P + GN_ROWS - 1) / GN_ROWS) * 2 * C; }
+size_t groupnorm_workspace(int F, int P, int C) { return (size_t)F * ((P + GN_ROWS - 1) / GN_ROWS) * 3 * C; }
 
 int groupnorm(const float *x, const float *w, const float *b, float *y, float *stats, int F, int P, int C, int groups, float eps, hipStream_t st, float *part,
               size_t part_floats) {

@@ -203,7 +203,13 @@ int edv_attn_spatial(const float *qkv_dev, float *out_dev, int32_t F, int32_t N,
                      size_t workspace_bytes, float *lse_dev, void *stream);
 /* lse_dev (optional, [F, heads, N]): per-row log-sum-exp of the scaled scores in base 2, the only extra state the
  * backward needs.  edv_attn_spatial_bwd: dqkv [F*N, 3*heads*64] (like qkv) from qkv, out, dout [F*N, heads*64] and lse;
- * delta_dev is [F, heads, N] floats of scratch. */
+ * delta_dev is [F, heads, N] floats of scratch.
+ * Accuracy: the probabilities are recomputed as 2^(S log2e - lse) from the fp32 lse, delta = dout . out comes from the forward's output.  Each
+ * probability so carries a relative error of about sqrt(32) ulp(lse) ln2 / sqrt(12) the forward's did not have, and a row of dS sums to zero only
+ * to that accuracy: per output column dq, dk, dv are within 4x of torch's fp32 autograd for |lse| up to about 16; with scores in the tens the
+ * largest dq error is about 10x torch's; a component kbar common to all keys enters dq as kbar sum_j dS_ij (1e-3 of dq at a score offset of 500
+ * with |kbar| = 62 |k - kbar|).  dk, dv and lse stay within 2x of torch.  Finite inputs; dout scaled by a power of two scales dqkv bit for bit;
+ * a NaN in a dout or k row of (frame f, head h) stays in the (f, h) block of dq, dk and dv. */
 /* The same attention with both products on the bf16 matrix pipe (EDV_PRODUCTS_BF16X6: three-term bf16 splits of q, k, v and of the probabilities,
  * six bf16 MFMAs per 16 k, fp32 accumulate and fp32 softmax; sequences longer than 128, shorter ones run the fp32 kernel).  Its own workspace size.
  * Input domain as for edv_gemm_x6: finite q, k, v with 2^-100 <= |x| <= 2^100 or exactly 0 (v scaled by a power of two scales the output bit for
@@ -229,7 +235,10 @@ int edv_rope_qk(float *qkv_dev, const float *table_dev, int32_t B, int32_t T, in
 
 /* GroupNorm(32 groups) on channels-last x [F,P,C] (motion_module.py:84,110).  With a workspace (edv_groupnorm_workspace bytes) the
  * statistics are taken in two coalesced stages (per 32-pixel chunk and channel, then merged per group with the parallel-variance
- * formula); with workspace_dev = NULL one workgroup per (frame, group) reads its strided slab twice.  Same values to fp32 rounding. */
+ * formula); with workspace_dev = NULL one workgroup per (frame, group) reads its strided slab twice.  Same values to fp32 rounding.
+ * Both paths take the variance in the corrected two-pass form (sum d^2 - (sum d)^2 / n about the fp32 mean, which is then corrected by sum d / n),
+ * so stats_dev = [F, groups, 2] (mean, rstd), which edv_groupnorm_bwd consumes, holds to fp32 rounding however far the mean is above the spread;
+ * a slab of one value v (at most 12 significant bits, chunks of a power-of-two number of rows) gives mean = v, rstd = rsqrt(eps), y = b exactly. */
 size_t edv_groupnorm_workspace(int32_t F, int32_t P, int32_t C);
 int edv_groupnorm(const float *x_dev, const float *w_dev, const float *b_dev, float *y_dev, float *stats_dev /* [F*32*2] scratch */,
                   int32_t F, int32_t P, int32_t C, int32_t groups, float eps, float *workspace_dev, size_t workspace_bytes, void *stream);

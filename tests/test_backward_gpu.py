@@ -84,6 +84,35 @@ def test_lora_gradients_match_oracle_autograd(lib, cuda, case):
     print(f"\n[{case}] {len(names)} tensors, worst scale-relative gradient error {worst:.2e}")
 
 
+def test_lora_gradients_with_outlier_channels(lib, cuda):
+    """The gradient counterpart of test_stages_with_outlier_channels_against_oracle: three channels of the position embedding x 50 (its constants),
+    so that every LayerNorm backward, qkv / fc1 weight-gradient product and attention backward of the encoder sees a residual stream with outlier
+    channels.  LoRA-factor gradients against the oracle's autograd in float64, the micro gate (2e-4 of each tensor's largest entry), in both
+    products modes; bf16 x 6 no worse than max(1.25 x the fp32 mode's error, 1e-6) per tensor.  The factor 50 needed no lowering.
+    Measured on an MI355X: 96 tensors, worst error 2.95e-5 in both modes (the training forward computes fp32 products whatever model.products says)."""
+    from tests.test_forward_gpu import OUTLIER_CHANNELS, OUTLIER_FACTOR
+
+    case = "micro_vda_dvlora"
+    model, kwargs, shape, _, _ = build_model(case)
+    with torch.no_grad():
+        model.pretrained.pos_embed[..., list(OUTLIER_CHANNELS)] *= OUTLIER_FACTOR
+    x = case_input(case)
+    names = set_trainable(model, FACTORS)
+    assert names
+    model = model.to(cuda).train()
+    gouts = upstream([(shape[0] * shape[1], 1, h, w) for (h, w) in model.output_shapes()])
+    ref, _ = oracle_grads(model, kwargs, x, names, gouts, dtype=torch.float64)
+    errs = {}
+    for products in ("f32", "bf16x6"):
+        model.products = products
+        hip, _ = hip_grads(model, x, names, gouts, cuda)
+        worst = check(hip, ref, 2e-4)
+        errs[products] = {n: (hip[n].cpu().double() - r).abs().max().item() / max(r.abs().max().item(), 1e-30) for n, r in ref.items()}
+        print(f"\n[{case}, outlier channels x{OUTLIER_FACTOR:g}, {products}] {len(names)} tensors, worst scale-relative gradient error {worst:.2e}")
+    for n, e6 in errs["bf16x6"].items():
+        assert e6 <= max(1.25 * errs["f32"][n], 1e-6), f"{n}: bf16x6 {e6:.3e} against f32 {errs['f32'][n]:.3e}"
+
+
 @pytest.mark.parametrize("case,head_key", [("micro_conv_dvlora", "head.conv_depth_"), ("micro_conv_invsig_ssb", "head.conv_depth_"),
                                            ("micro_vda_dvlora", "head.scratch.output_conv"), ("micro_clstoken_nocls", "head.conv_depth_")],
                          ids=["conv_head", "conv_head_inv_sigmoid_ssb", "vda_train_output_conv", "conv_head_use_clstoken_no_cls_token"])
