@@ -82,6 +82,26 @@ int edv_conv3x3_ws(const float *x_dev, const float *wpacked_dev, const float *bi
                         workspace_bytes, stream);
 }
 
+int edv_set_conv_impl(int32_t mode) {
+    EDV_CHECK(mode >= 0 && mode <= 2, "edv_set_conv_impl: mode 0 (automatic), 1 (never fused) or 2 (fused wherever supported)");
+    set_conv_impl(mode);
+    return 0;
+}
+
+int edv_conv3x3_dot(const float *x_dev, const float *wpacked_dev, const float *bias_dev, float *y_dev, int32_t F, int32_t H, int32_t W, int32_t Cin,
+                    int32_t Cout, int32_t stride, int32_t pre_relu, int32_t post_relu, const float *w2_dev, const float *b2_dev, int32_t act2, void *stream) {
+    EDV_CHECK(F > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "empty problem");
+    EDV_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
+    EDV_CHECK(conv_dot_enabled(), "edv_conv3x3_dot: the fused epilogue is switched off (edv_set_conv_impl(1) or EDV_CONV_DOT=0)");
+    GemmDesc g;
+    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+    g.A = x_dev; g.W = wpacked_dev; g.ldw = 9 * Cin; g.ldc = Cout; g.M = (long long)F * OH * OW; g.N = Cout; g.K = 9 * Cin;
+    g.bias = bias_dev; g.act = post_relu ? ACT_RELU : ACT_NONE;
+    g.loader = LOAD_CONV3; g.cH = H; g.cW = W; g.cC = Cin; g.cOH = OH; g.cOW = OW; g.cS = stride; g.pre_relu = pre_relu ? 1 : 0;
+    g.w2 = w2_dev; g.b2 = b2_dev; g.act2 = act2; g.dot_out = y_dev;
+    return conv_dot(g, (hipStream_t)stream);
+}
+
 int edv_pack_conv3x3(const float *w_dev, float *wpacked_dev, int32_t Cout, int32_t Cin, void *stream) {
     return pack_conv3x3(w_dev, wpacked_dev, Cout, Cin, (hipStream_t)stream);
 }

@@ -15,6 +15,7 @@
 // out-of-range lane of a buffer LDS-DMA writes zeros into LDS (checked on the part, scratch/ubench/README), so no zero page is read.
 // What is left per k-tile: one compare + select per A-side DMA (is this lane's tap inside the image?) and, with pre_relu, the v_max of
 // the A fragments.
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -173,9 +174,17 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
 
         EpiCols<1> cols;
         if (EP != 0) cols = gemm_epilogue_prefetch<1>(g, n0, wn * 32, l31);
+        float w2v = 0.f, b2v = 0.f;  // EP >= 8 (the fused 1x1, gemm_common.hpp): the lane's column of w2, and b2
+        if constexpr (EP >= 8) {
+            w2v = g.w2[n0 + l31 < g.N ? n0 + l31 : g.N - 1];
+            if (g.b2) b2v = g.b2[0];
+        }
         f32x16 acc[1][1];
         auto epilogue = [&]() {
-            if constexpr (BUF && EP >= 1 && EP <= 3)  // addresses in scalar registers, edge rows / columns masked by the descriptor (gemm_common.hpp)
+            if constexpr (EP >= 8) {
+                static_assert(EP < 8 || (WGM == 4 && BUF && !SPLIT), "the fused 1x1 needs every column of a row in one wave, and 32-bit offsets");
+                gemm_epilogue_dot<EP - 8>(g, acc[0][0], cols, w2v, b2v, m0 + wave_s * 32, n0, l31, lh);
+            } else if constexpr (BUF && EP >= 1 && EP <= 3)  // addresses in scalar registers, edge rows / columns masked by the descriptor (gemm_common.hpp)
                 gemm_epilogue_buf<EP - 1>(g, acc[0][0], cols, m0 + (wave_s / WGN) * 32, n0 + (wave_s % WGN) * 32, l31, lh);
             else
                 gemm_epilogue_ep<1, 1, STORE_ROWS, EP>(g, acc, cols, m0, n0, wm * 32, wn * 32, l31, lh);
@@ -314,7 +323,36 @@ int launch_conv(const GemmDesc &d, hipStream_t st) {
     }
 }
 
+// process-wide implementation switch (edv_set_conv_impl)
+std::atomic<int> g_conv_impl{0};
+
+// the operand limits of BUF = true (launch_conv_ep) for a launch without C / R1 / R2, plus the one-float-per-row output
+bool dot_fits_buffer(const GemmDesc &d) {
+    const long long frames = (d.M - 1) / ((long long)d.cOH * d.cOW) + 1;
+    return frames * d.cH * d.cW * d.cC * 4 < (1ll << 31) - (1 << 20) && (long long)d.N * d.ldw * 4 < (1ll << 32) - (1 << 20) && (d.M + 128) * 4 < (1ll << 32) - (1 << 20);
+}
+
+template <int EP>
+int launch_conv_dot(const GemmDesc &d, hipStream_t st) {
+    const long long tiles = (d.M + 127) / 128;
+    EDV_CHECK(tiles > 0 && tiles < (1ll << 31), "bad grid");
+    GemmSplit sp{};
+    long long grid;
+    plan_plain(tiles, conv_dma_split_policy(), &sp, &grid);
+    EDV_LAUNCH((conv3_dma_kernel<4, EP, false, true>), dim3((unsigned)grid), dim3(256), 0, st, d, sp);
+    EDV_LAUNCH_OK();
+    return 0;
+}
+
 }  // namespace
+
+void set_conv_impl(int mode) { g_conv_impl.store(mode < 0 || mode > 2 ? 0 : mode, std::memory_order_relaxed); }
+int conv_impl() { return g_conv_impl.load(std::memory_order_relaxed); }
+bool conv_dot_enabled() {
+    // EDV_CONV_DOT=0: never fuse the 1x1 into the convolution (A/B runs).  Read at every call -- a few per forward -- and not cached like the other
+    // flags: tests/test_conv_halo_gpu.py switches it inside one process to compare the halo kernel alone with the parent's path bit for bit.
+    return conv_impl() != 1 && env_int("EDV_CONV_DOT", 1) != 0;
+}
 
 // Which launches split: grids that do not fill the part and whose tiles are deep (Cin >= 192: 54+ k-tiles), or that leave most of it idle (8 tiles
 // per resident slot).  Measured (scratch/kb_conv_split.py, plain / split us): layer4_rn 46 tiles x 108 k-tiles 91 / 31, resize_layers.3
@@ -330,10 +368,25 @@ bool conv_dma_supported(const GemmDesc &d) {
     return d.loader == LOAD_CONV3 && d.store == STORE_ROWS && d.cC % CBK == 0 && d.K == 9 * d.cC && d.ldw % 4 == 0 && d.M > 0 && d.N > 0;
 }
 
+bool conv_dot_supported(const GemmDesc &d) {
+    return conv_dma_supported(d) && d.N <= 32 && (d.act == ACT_NONE || d.act == ACT_RELU) && d.act2 != ACT_GELU && d.act2 >= ACT_NONE && d.act2 <= ACT_SIGMOID_NEG &&
+           !d.gamma && !d.R1 && !d.R2 && !d.P1 && d.c_map.period == 0 && dot_fits_buffer(d);
+}
+
+// The convolution with the 1x1 to one channel in its epilogue: the plain grid of conv3_dma_kernel<4, ...> (every launch this serves fills the part).
+int conv_dot(const GemmDesc &d, hipStream_t st) {
+    EDV_CHECK(d.A && d.W && d.w2 && d.dot_out, "null operand");
+    EDV_CHECK(conv_dot_supported(d), "fused 1x1 epilogue: Cin % 32 == 0, Cout <= 32, post-activation none / ReLU, no residual, operands below 2 GB");
+    EDV_CHECK(((uintptr_t)d.A % 16 == 0) && ((uintptr_t)d.W % 16 == 0), "A/W must be 16-byte aligned");
+    if (conv_halo_wanted(d)) return conv_halo(d, st);
+    return d.act == ACT_RELU ? launch_conv_dot<8 + ACT_RELU>(d, st) : launch_conv_dot<8 + ACT_NONE>(d, st);
+}
+
 int conv_dma(const GemmDesc &d, hipStream_t st) {
     EDV_CHECK(d.A && d.W && d.C, "null operand");
     EDV_CHECK(conv_dma_supported(d), "LDS-DMA convolution needs Cin % 32 == 0");
     EDV_CHECK(((uintptr_t)d.A % 16 == 0) && ((uintptr_t)d.W % 16 == 0), "A/W must be 16-byte aligned");
+    if (conv_halo_wanted(d)) return conv_halo(d, st);
     return d.N <= 32 ? launch_conv<4>(d, st) : launch_conv<2>(d, st);
 }
 

@@ -690,7 +690,6 @@ struct Forward : Run {
         float *o1, *up, *o2;
         EDV_TRY(wsbuf(tg + "o1", cap_in * Fh, &o1));
         EDV_TRY(wsbuf(tg + "up", cap_out * Fh, &up));
-        EDV_TRY(wsbuf(tg + "o2", cap_out * 32, &o2));
         const float *wt, *b;
         EDV_TRY(packedw(c1 + ".weight", &wt));
         EDV_TRY(param(c1 + ".bias", &b));
@@ -699,6 +698,25 @@ struct Forward : Run {
             HbmScope b_(c, KC_BILINEAR, st, 4.0 * (double)F * Fh * ((double)h * w + (double)oh * ow));
             EDV_TRY(bilinear(o1, up, F, h, w, Fh, oh, ow, ACT_NONE, st));
         }
+        // Inference: the 1x1 rides in the epilogue of the second convolution (conv_dma.hip, conv_dot) -- o2 is neither allocated nor written and the
+        // dot_channels launch goes.  Training keeps the two steps: the backward reads o2.
+        GemmDesc gd;
+        gd.A = up; gd.ldw = 9 * Fh; gd.ldc = 32; gd.M = (long long)F * oh * ow; gd.N = 32; gd.K = 9 * Fh; gd.act = ACT_RELU; gd.act2 = act; gd.dot_out = out;
+        gd.loader = LOAD_CONV3; gd.cH = oh; gd.cW = ow; gd.cC = Fh; gd.cOH = oh; gd.cOW = ow; gd.cS = 1;
+        if (!c->train && conv_dot_enabled() && conv_dot_supported(gd)) {
+            EDV_TRY(packedw(c2 + ".weight", &gd.W));
+            EDV_TRY(param(c2 + ".bias", &gd.bias));
+            EDV_TRY(param(c3 + ".weight", &gd.w2));
+            EDV_TRY(param(c3 + ".bias", &gd.b2));
+            c->launches += 2;  // the bilinear above and this one
+            if (c->prof_mask & (1u << KC_CONV3)) {  // as conv3() counts a launch, with one float per pixel written
+                c->prof_flops[KC_CONV3] += 2.0 * (double)gd.M * gd.N * gd.K;
+                c->prof_bytes[KC_CONV3] += 4.0 * ((double)gd.M * Fh + (double)gd.N * gd.K + (double)gd.M);
+            }
+            Bracket b_(c, KC_CONV3, st);
+            return conv_dot(gd, st);
+        }
+        EDV_TRY(wsbuf(tg + "o2", cap_out * 32, &o2));
         EDV_TRY(packedw(c2 + ".weight", &wt));
         EDV_TRY(param(c2 + ".bias", &b));
         EDV_TRY(conv3(up, oh, ow, Fh, wt, b, 32, 1, o2, false, ACT_RELU));

@@ -318,6 +318,59 @@ __device__ __forceinline__ void gemm_epilogue_buf(const GemmDesc &g, f32x16 &acc
     }
 }
 
+// Fused 1x1 to one channel (GemmDesc::w2; EP = 8 + ACT in conv_dma.hip) for a wave that holds ALL columns of its 32 rows (one column tile, N <= 32):
+//   y[row] = act2(sum_n w2[n] * act(acc[row][n] + bias[n]) + b2),  one float per row instead of the N-wide tile.
+// A lane holds column l31 of 16 rows, so the sum over n is a sum over the 32 lanes of a wave half, taken in registers: v_permlane16_swap
+// (gfx950) exchanges the odd 16-lane rows of one register with the even rows of its neighbour, so one swap + one add folds lanes l and l ^ 16 of TWO
+// registers into one (even rows: register 2i, odd rows: register 2i + 1); four DPP adds (quad swaps, half-row mirror, row mirror) finish
+// each of the eight.  No LDS, no barrier: 8 swaps + 40 adds for 16 rows.  Every lane of a 16-lane row then holds the row's sum; lane i < 8 of it
+// keeps register i and stores that row's value.  w2v, b2v: the lane's w2[n] (any value for n >= N: those lanes add 0) and b2, fetched before the k loop.
+// gemm_dot_reduce returns the lane's value: for lane i = l31 & 15 < 8 the finished y of accumulator register r = 2 i + (l31 >> 4), i.e. of row
+// (r & 3) + 8 (r >> 2) + 4 lh of the wave's block; lanes 8..15 of a 16-lane row hold nothing to store.  Shared by conv_dma.hip and conv_halo.hip.
+template <int ACT>
+__device__ __forceinline__ float gemm_dot_reduce(const GemmDesc &g, const f32x16 &acc, const EpiCols<1> &cols, float w2v, float b2v, bool col_in, int l31) {
+    float t[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float v = acc[r] + cols.bias[0];
+        if (ACT == ACT_RELU) v = fmaxf(v, 0.0f);
+        t[r] = col_in ? w2v * v : 0.f;
+    }
+    float s[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(t[2 * i]), __float_as_uint(t[2 * i + 1]), false, false);
+        float v = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+        v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]: lane ^ 1
+        v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]: lane ^ 2
+        v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x141, 0xf, 0xf, true));  // row_half_mirror: the other quad of 8
+        v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x140, 0xf, 0xf, true));  // row_mirror: the other half of 16
+        s[i] = v;
+    }
+    const int i = l31 & 15;
+    float v = s[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) v = i == k ? s[k] : v;
+    v += b2v;
+    if (g.act2 == ACT_RELU) v = fmaxf(v, 0.f);
+    else if (g.act2 == ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+    else if (g.act2 == ACT_SIGMOID_NEG) v = 1.f / (1.f + expf(v));
+    return v;
+}
+
+// ... and its store for a wave whose 32 rows are consecutive rows of M from row0 (conv3_dma_kernel)
+template <int ACT>
+__device__ __forceinline__ void gemm_epilogue_dot(const GemmDesc &g, f32x16 &acc, const EpiCols<1> &cols, float w2v, float b2v, long long row0, int col0, int l31,
+                                                  int lh) {
+    const float v = gemm_dot_reduce<ACT>(g, acc, cols, w2v, b2v, col0 + l31 < g.N, l31);
+    const int i = l31 & 15, r = 2 * i + (l31 >> 4);
+    const unsigned row = (unsigned)((r & 3) + 8 * (r >> 2) + 4 * lh);
+    // descriptor ends at row M: rows past it (an edge tile) are dropped, as in gemm_epilogue_buf
+    const auto ro = __builtin_amdgcn_make_buffer_rsrc(g.dot_out, 0, (int)(unsigned)(g.M * 4), 0x00020000);
+    const unsigned vo = i < 8 ? row * 4u : 0xfffff000u;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ro, (int)vo, (int)(unsigned)(row0 * 4), EDV_EPI_STORE_AUX);
+}
+
 // EP = 5 (see epilogue_kind): rows m = mb + dr of a 32-row block cross at most one period boundary, so one division per block suffices
 template <int FM, int FN>
 __device__ __forceinline__ void gemm_epilogue_mapped(const GemmDesc &g, f32x16 (&acc)[FM][FN], const EpiCols<FN> &cols, long long m0, int n0, int wrow,

@@ -56,6 +56,12 @@ struct GemmDesc {
     size_t ws_floats = 0;
     // bf16 planes [3][N][K] of W (gemm_x6_split): with them a dense STORE_ROWS GEMM runs its products on the bf16 matrix pipe (gemm_x6.hip)
     const void *Wx6 = nullptr;
+    // fused 1x1 to one channel behind a LOAD_CONV3 launch with N <= 32 (conv_dma.hip, conv_dot): with w2 [N] set, the tile is not stored;
+    // dot_out[c_row] = act2(sum_n w2[n] * act(acc + bias[n]) + b2[0]) is, one float per output pixel (b2 may be null; act2: any ACT_* but GELU).
+    // C, gamma, R1, R2 and P1 are not used.
+    const float *w2 = nullptr, *b2 = nullptr;
+    float *dot_out = nullptr;
+    int act2 = ACT_NONE;
 };
 int gemm(const GemmDesc &d, hipStream_t st);
 // "bf16 x 6" GEMM (gemm_x6.hip): fp32 in / out, six bf16 MFMAs per product term set, error below fp32's unit roundoff per term
@@ -73,6 +79,17 @@ int gemm_dma(const GemmDesc &d, hipStream_t st);
 // LDS-DMA implicit-GEMM 3x3 convolution (conv_dma.hip): Cin % 32 == 0, any stride the GemmDesc allows
 bool conv_dma_supported(const GemmDesc &d);
 int conv_dma(const GemmDesc &d, hipStream_t st);
+// the same launch with the fused 1x1 epilogue (GemmDesc::w2): Cout <= 32, post-activation none / ReLU, operands within the 32-bit offset limits
+bool conv_dot_supported(const GemmDesc &d);
+int conv_dot(const GemmDesc &d, hipStream_t st);
+// halo-tiled variant (conv_halo.hip): stride 1, Cin 32 or 64, Cout <= 32; the stored tile or, with GemmDesc::w2, the fused 1x1.  Same bits as conv_dma.
+bool conv_halo_supported(const GemmDesc &d);
+bool conv_halo_wanted(const GemmDesc &d);  // supported, and chosen by the mode (edv_set_conv_impl, EDV_CONV_HALO) or the measured table
+int conv_halo(const GemmDesc &d, hipStream_t st);
+// process-wide choice of the convolution implementation (edv_set_conv_impl): 0 automatic, 1 never halo / fused, 2 both wherever supported
+void set_conv_impl(int mode);
+int conv_impl();
+bool conv_dot_enabled();  // conv_impl() != 1 and not EDV_CONV_DOT=0
 // the split policies the three launchers above run with (streamk_plan.hpp); edv_split_plan runs the planner on them without a device
 const SplitPolicy &gemm_dma_split_policy();
 const SplitPolicy &gemm_x6_split_policy();

@@ -190,6 +190,23 @@ int edv_conv3x3(const float *x_dev, const float *wpacked_dev, const float *bias_
 int edv_conv3x3_ws(const float *x_dev, const float *wpacked_dev, const float *bias_dev, float *y_dev, int32_t F, int32_t H, int32_t W,
                    int32_t Cin, int32_t Cout, int32_t stride, int32_t pre_relu, int32_t post_relu, const float *R1_dev,
                    const float *R2_dev, float *workspace_dev, size_t workspace_bytes, void *stream);
+/* Additive entry points (the ABI version stays as it is: the rule stated at edv_ingest_u8).
+ * edv_conv3x3_dot: edv_conv3x3 followed by a 1x1 convolution to ONE channel and its activation, in one launch:
+ *   y[f,oy,ox] = act2(sum_c w2[c] * act(conv(x)[f,oy,ox,c] + bias[c]) + b2[0]),   y [F,OH,OW]
+ * -- the Cout-wide tensor is never written.  Cout <= 32, Cin % 32 == 0, no residuals; b2_dev may be NULL; act2: 0 none, 2 ReLU, 3 sigmoid(z),
+ * 4 sigmoid(-z) (the modes of edv_dot_channels).  The sum over c is taken in a fixed order that differs from edv_dot_channels': the two agree to
+ * within the rounding of a 32-term fp32 sum, not bit for bit.  A shape outside these limits, or a process in which the fused epilogue is switched
+ * off (below), is an error: the caller runs edv_conv3x3 + edv_dot_channels instead.
+ * edv_set_conv_impl: process-wide choice for the 3x3 convolutions and the engine's output heads.  0 = automatic (the default): the halo-tiled
+ * kernel (conv_halo.hip: stride 1, Cin 32 or 64, Cout <= 32; bit-identical to the im2col kernel) for the shape classes where it measured
+ * faster, the fused epilogue wherever it is supported; 1 = neither: every convolution runs the im2col kernel and stores its tile, the heads
+ * run edv_dot_channels' kernel behind it; 2 = both wherever supported, whatever the table says (tests, A/B runs).  The environment variables
+ * EDV_CONV_HALO=0 and EDV_CONV_DOT=0 switch either off for a whole process.  A training forward never fuses: the backward reads the
+ * 32-channel tensor. */
+int edv_set_conv_impl(int32_t mode);
+int edv_conv3x3_dot(const float *x_dev, const float *wpacked_dev, const float *bias_dev, float *y_dev, int32_t F, int32_t H, int32_t W,
+                    int32_t Cin, int32_t Cout, int32_t stride, int32_t pre_relu, int32_t post_relu, const float *w2_dev,
+                    const float *b2_dev, int32_t act2, void *stream);
 /* Repack a torch Conv2d weight [Cout,Cin,3,3] to [Cout][3][3][Cin]. */
 int edv_pack_conv3x3(const float *w_dev, float *wpacked_dev, int32_t Cout, int32_t Cin, void *stream);
 
