@@ -140,6 +140,11 @@ SIGNATURES = {
     "edv_render_workspace": (C.c_size_t, [_i64]),
     "edv_render_range": (C.c_int, [_fp, _i64, _i32, _i32, _i32, _i64, _i64, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_render_colorize": (C.c_int, [_fp, _i64, _i32, _i32, _fp, _i32, _f32, _i32, _fp, _fp, _fp, C.c_void_p]),
+    # point clouds on the device (additive, ABI stays 15): both calls take one CloudSelection
+    "edv_cloud_tile_pixels": (_i32, []),
+    "edv_cloud_workspace": (C.c_size_t, [_i64, _i32, _i32, _i32]),
+    "edv_cloud_count": (C.c_int, [C.c_void_p, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_cloud_scatter": (C.c_int, [C.c_void_p, _fp, _i32, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _i64, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),
@@ -231,6 +236,12 @@ class TrainerLossWeights(C.Structure):
 class TrainerLossGrads(C.Structure):
     _fields_ = [("disp", C.c_void_p * 4), ("refined", (C.c_void_p * 2) * 4), ("transform", (C.c_void_p * 2) * 4), ("K", C.c_void_p), ("invK", C.c_void_p),
                 ("T", C.c_void_p * 2)]
+
+
+class CloudSelection(C.Structure):
+    """edv_cloud_selection (include/endodav_hip.h): which pixels of a clip are kept and at what depth."""
+    _fields_ = [("x_dev", C.c_void_p), ("n", _i64), ("h", _i32), ("w", _i32), ("step", _i32), ("mode", _i32), ("lo", _f32), ("span", _f32), ("gain", _f32),
+                ("near_z", _f32), ("far_z", _f32), ("mask_dev", C.c_void_p), ("mask_stride", _i64)]
 
 
 class GemmDescC(C.Structure):

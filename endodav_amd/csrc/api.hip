@@ -289,6 +289,24 @@ int edv_render_colorize(const float *x_dev, int64_t n, int32_t h, int32_t w, con
     return render_colorize(x_dev, n, h, w, range_dev, range_stride, eps, clip, lut_dev, beside_dev, out_dev, (hipStream_t)stream);
 }
 
+namespace {
+CloudSel cloud_sel(const edv_cloud_selection &s) {
+    return CloudSel{s.x_dev, s.n, s.h, s.w, s.step, s.mode, s.lo, s.span, s.gain, s.near_z, s.far_z, s.mask_dev, s.mask_stride};
+}
+}  // namespace
+int32_t edv_cloud_tile_pixels(void) { return cloud_tile_pixels(); }
+size_t edv_cloud_workspace(int64_t n, int32_t h, int32_t w, int32_t step) { return cloud_workspace(n, h, w, step); }
+int edv_cloud_count(const edv_cloud_selection *sel, int64_t *offsets_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    EDV_CHECK(sel, "null selection");
+    return cloud_count(cloud_sel(*sel), reinterpret_cast<long long *>(offsets_dev), workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+int edv_cloud_scatter(const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, const uint8_t *frames_dev, const int64_t *offsets_dev,
+                      const void *workspace_dev, size_t workspace_bytes, float *points_dev, uint8_t *colors_dev, int64_t capacity, void *stream) {
+    EDV_CHECK(sel, "null selection");
+    return cloud_scatter(cloud_sel(*sel), cams_dev, cam_stride, frames_dev, reinterpret_cast<const long long *>(offsets_dev), workspace_dev, workspace_bytes,
+                         points_dev, colors_dev, capacity, (hipStream_t)stream);
+}
+
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream) {

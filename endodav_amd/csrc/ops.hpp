@@ -152,6 +152,21 @@ size_t render_workspace(long long n);  // bytes
 int render_range(const float *x, long long n, int h, int w, int mode, long long rank_lo, long long rank_hi, float *range, void *ws, size_t ws_bytes, hipStream_t stream);
 int render_colorize(const float *x, long long n, int h, int w, const float *range, int range_stride, float eps, int clip, const uint8_t *lut, const uint8_t *beside,
                     uint8_t *out, hipStream_t stream);
+// point clouds on the device (pointcloud.hip): which pixels of a clip x [n, h, w] are kept and at what depth (edv_cloud_selection), counted and
+// scanned by cloud_count, lifted through cams [1 or n][21] doubles and compacted in order by cloud_scatter
+struct CloudSel {
+    const float *x;
+    long long n;
+    int h, w, step, mode;
+    float lo, span, gain, near_z, far_z;
+    const uint8_t *mask;
+    long long mask_stride;
+};
+int cloud_tile_pixels();  // output pixels per workgroup, 8 workspace bytes each
+size_t cloud_workspace(long long n, int h, int w, int step);  // bytes; 0 for a shape the calls refuse
+int cloud_count(const CloudSel &s, long long *offsets, void *ws, size_t ws_bytes, hipStream_t stream);
+int cloud_scatter(const CloudSel &s, const double *cams, int cam_stride, const uint8_t *frames, const long long *offsets, const void *ws, size_t ws_bytes,
+                  float *points, uint8_t *colors, long long capacity, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

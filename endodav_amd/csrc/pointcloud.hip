@@ -1,0 +1,281 @@
+// Point clouds on the device: a clip of depth [n, h, w] fp32 lifted to world-space points with the frames' colours, masked, subsampled and
+// compacted in order (get_point_cloud of the loaders in tools/viser-rgbd/utils and visualize_reconstruction.py in the reference, float64 numpy there).
+// An order-preserving stream compaction with the geometry fused in, three launches in two calls:
+//   cloud_count    one workgroup per tile of CLOUD_TILE output pixels of one frame (the frame is blockIdx.y): the kept pixels of the tile, counted
+//                  by wave ballot and popcount, one 64-bit count per tile in the workspace
+//                  one workgroup: exclusive 64-bit scan of the counts over all tiles in frame-major order, in place; offsets[f] = the points of
+//                  the frames before f, offsets[n] = the total
+//   cloud_scatter  the same tiles: the predicate again, the rank of every kept pixel inside its tile (ballot and lane prefix in a wave, an LDS
+//                  prefix over waves and iterations), the point in fp64, and element stores of point g = tile offset + rank when g < capacity
+// No workgroup waits for another inside a launch and there are no atomics at all: the same input gives the same bits on every call.  The output
+// of a tile starts at an arbitrary 12-byte (points) or 1-byte (colours) boundary; every store is one float or one byte of exactly one point, so
+// no two workgroups ever write the same dword.
+// Contraction is off for the whole file and the division is IEEE's: every fp32 and fp64 operation is numpy's, in the order written here.
+#include <algorithm>
+
+#include "ops.hpp"
+
+#pragma clang fp contract(off)
+
+namespace edv {
+namespace {
+
+using u64 = unsigned long long;
+
+constexpr int CLOUD_THREADS = 256, CLOUD_WAVES = CLOUD_THREADS / WAVE;
+constexpr int CLOUD_ITERS = 8;
+constexpr int CLOUD_TILE = CLOUD_THREADS * CLOUD_ITERS;  // output pixels per workgroup: the one constant behind cloud_tile_pixels()
+constexpr int SCAN_THREADS = 1024, SCAN_WAVES = SCAN_THREADS / WAVE, SCAN_ITEMS = 4;
+
+// output pixel q = oy * ow + ox of the subsampled grid -> the source pixel that holds the grid position ((ox + 0.5) * step, (oy + 0.5) * step)
+__device__ __forceinline__ int source_pixel(const CloudSel &s, int ow, unsigned q, int &ox, int &oy) {
+    oy = (int)(q / (unsigned)ow), ox = (int)(q - (unsigned)oy * (unsigned)ow);
+    const long long sy = min((long long)oy * s.step + s.step / 2, (long long)s.h - 1);
+    const long long sx = min((long long)ox * s.step + s.step / 2, (long long)s.w - 1);
+    return (int)(sy * s.w + sx);  // h * w < 2^31
+}
+
+__device__ __forceinline__ float depth_value(const CloudSel &s, float x) {
+    if (s.mode == 0) return x * s.gain;
+    const float scaled = s.lo + s.span * x;
+    const float z = 1.0f / scaled;
+    return z * s.gain;
+}
+
+// NaN fails both comparisons, +Inf fails z < far even for far = +Inf
+__device__ __forceinline__ bool kept(const CloudSel &s, float x, unsigned m, float &z) {
+    z = depth_value(s, x);
+    return m != 0 && z > s.near_z && z < s.far_z;
+}
+
+// grid (tiles per frame, frames).  UNIT: step == 1, where the source pixel is the output pixel
+template <bool UNIT>
+__global__ __launch_bounds__(CLOUD_THREADS) void cloud_count_kernel(CloudSel s, int ow, unsigned grid_pixels, u64 *__restrict__ counts) {
+    __shared__ unsigned red[CLOUD_WAVES];
+    const long long f = blockIdx.y;
+    const float *xf = s.x + f * s.h * s.w;
+    const uint8_t *mf = s.mask ? s.mask + f * s.mask_stride : nullptr;
+    // all loads of the tile first, so that they are in flight together
+    float x[CLOUD_ITERS];
+    unsigned m[CLOUD_ITERS];
+#pragma unroll
+    for (int it = 0; it < CLOUD_ITERS; ++it) {
+        const unsigned q = blockIdx.x * (unsigned)CLOUD_TILE + it * CLOUD_THREADS + threadIdx.x;
+        x[it] = 0.0f, m[it] = 0;
+        if (q < grid_pixels) {
+            int ox, oy;
+            const int p = UNIT ? (int)q : source_pixel(s, ow, q, ox, oy);
+            x[it] = xf[p], m[it] = mf ? mf[p] : 1u;
+        }
+    }
+    unsigned c = 0;
+#pragma unroll
+    for (int it = 0; it < CLOUD_ITERS; ++it) {
+        float z;
+        c += (unsigned)__popcll(__ballot(kept(s, x[it], m[it], z)));
+    }
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    if (lane == 0) red[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int v = 0; v < CLOUD_WAVES; ++v) t += red[v];
+        counts[f * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// one workgroup: ws[i] = sum of ws[0 .. i) for the `tiles` counts, offsets[f] = ws[f * tiles_per_frame] after the scan, offsets[n] = the total
+__global__ __launch_bounds__(SCAN_THREADS) void cloud_scan_kernel(u64 *__restrict__ ws, long long tiles, long long tiles_per_frame, long long *__restrict__ offsets,
+                                                                  long long n) {
+    __shared__ u64 wave_sum_s[SCAN_WAVES];
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    u64 carry = 0;
+    for (long long base = 0; base < tiles; base += (long long)SCAN_THREADS * SCAN_ITEMS) {
+        const long long i0 = base + (long long)threadIdx.x * SCAN_ITEMS;
+        u64 v[SCAN_ITEMS], mine = 0;
+#pragma unroll
+        for (int j = 0; j < SCAN_ITEMS; ++j) {
+            v[j] = i0 + j < tiles ? ws[i0 + j] : 0;
+            mine += v[j];
+        }
+        u64 inc = mine;  // inclusive over the lanes of the wave
+#pragma unroll
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const u64 up = __shfl_up(inc, o, WAVE);
+            if (lane >= o) inc += up;
+        }
+        if (lane == WAVE - 1) wave_sum_s[wave] = inc;
+        __syncthreads();
+        u64 before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < SCAN_WAVES; ++k) {
+            const u64 t = wave_sum_s[k];
+            before += k < wave ? t : 0;
+            total += t;
+        }
+        u64 ex = carry + before + (inc - mine);
+#pragma unroll
+        for (int j = 0; j < SCAN_ITEMS; ++j) {
+            const long long i = i0 + j;
+            if (i < tiles) {
+                ws[i] = ex;
+                if (i % tiles_per_frame == 0) offsets[i / tiles_per_frame] = (long long)ex;
+                ex += v[j];
+            }
+        }
+        carry += total;
+        __syncthreads();  // wave_sum_s is rewritten by the next round
+    }
+    if (threadIdx.x == 0) offsets[n] = (long long)carry;
+}
+
+// grid (tiles per frame, frames)
+__global__ __launch_bounds__(CLOUD_THREADS) void cloud_scatter_kernel(CloudSel s, int ow, unsigned grid_pixels, const double *__restrict__ cams, int cam_stride,
+                                                                      const uint8_t *__restrict__ frames, const long long *__restrict__ offsets,
+                                                                      const u64 *__restrict__ tile_offsets, float *__restrict__ points,
+                                                                      uint8_t *__restrict__ colors, u64 capacity) {
+    __shared__ unsigned cnt[CLOUD_ITERS][CLOUD_WAVES];
+    const long long f = blockIdx.y;
+    const u64 tile_base = tile_offsets[f * gridDim.x + blockIdx.x];
+    // uniform over the workgroup: a frame without points, or a tile that starts behind the capacity, has nothing to write
+    if (offsets[f + 1] == offsets[f] || tile_base >= capacity) return;
+    const float *xf = s.x + f * s.h * s.w;
+    const uint8_t *mf = s.mask ? s.mask + f * s.mask_stride : nullptr;
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    float z[CLOUD_ITERS];
+    unsigned m[CLOUD_ITERS];
+    int p[CLOUD_ITERS], ox[CLOUD_ITERS], oy[CLOUD_ITERS];
+    u64 ballot[CLOUD_ITERS];
+#pragma unroll
+    for (int it = 0; it < CLOUD_ITERS; ++it) {  // all loads of the tile first, so that they are in flight together
+        const unsigned q = blockIdx.x * (unsigned)CLOUD_TILE + it * CLOUD_THREADS + threadIdx.x;
+        z[it] = 0.0f, m[it] = 0, p[it] = 0, ox[it] = 0, oy[it] = 0;
+        if (q < grid_pixels) {
+            p[it] = source_pixel(s, ow, q, ox[it], oy[it]);
+            z[it] = xf[p[it]], m[it] = mf ? mf[p[it]] : 1u;
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < CLOUD_ITERS; ++it) {
+        ballot[it] = __ballot(kept(s, z[it], m[it], z[it]));
+        if (lane == 0) cnt[it][wave] = (unsigned)__popcll(ballot[it]);
+    }
+    __syncthreads();
+    // rank of the first kept pixel of (iteration, wave): pixels are ordered by iteration, then wave, then lane
+    unsigned first[CLOUD_ITERS] = {}, run = 0;
+#pragma unroll
+    for (int it = 0; it < CLOUD_ITERS; ++it) {
+#pragma unroll
+        for (int v = 0; v < CLOUD_WAVES; ++v) {
+            if (v == wave) first[it] = run;
+            run += cnt[it][v];
+        }
+    }
+    if (run == 0) return;
+    const double *cam = cams + f * cam_stride;
+    double Kinv[9], R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Kinv[i] = cam[i], R[i] = cam[9 + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = cam[18 + i];
+    const bool colour = frames && colors;
+    const uint8_t *ff = colour ? frames + f * s.h * s.w * 3 : nullptr;
+    const u64 below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int it = 0; it < CLOUD_ITERS; ++it) {
+        if (!((ballot[it] >> lane) & 1ull)) continue;
+        const u64 g = tile_base + first[it] + (unsigned)__popcll(ballot[it] & below);
+        if (g >= capacity) continue;
+        const double u = ((double)ox[it] + 0.5) * (double)s.step, v = ((double)oy[it] + 0.5) * (double)s.step;
+        double l[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) l[i] = (Kinv[3 * i] * u + Kinv[3 * i + 1] * v) + Kinv[3 * i + 2];
+        const double zd = (double)z[it];
+        float *o = points + g * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double r = (R[3 * i] * l[0] + R[3 * i + 1] * l[1]) + R[3 * i + 2] * l[2];
+            o[i] = (float)(t[i] + r * zd);
+        }
+        if (colour) {
+            const uint8_t *c = ff + (long long)p[it] * 3;
+            uint8_t *oc = colors + g * 3;
+            oc[0] = c[0], oc[1] = c[1], oc[2] = c[2];
+        }
+    }
+}
+
+inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+struct CloudGrid {
+    int ow;
+    unsigned pixels;  // oh * ow <= h * w < 2^31
+    long long tiles_per_frame;
+};
+
+inline CloudGrid cloud_grid(int h, int w, int step) {
+    const long long oh = ((long long)h + step - 1) / step, ow = ((long long)w + step - 1) / step;
+    return {(int)ow, (unsigned)(oh * ow), (oh * ow + CLOUD_TILE - 1) / CLOUD_TILE};
+}
+
+inline int check_selection(const CloudSel &s) {
+    EDV_CHECK(s.x, "null depth");
+    EDV_CHECK(s.n >= 1 && s.n <= 65535, "n must be in 1..65535");
+    EDV_CHECK(s.h >= 1 && s.w >= 1 && s.step >= 1, "h, w and step must be at least 1");
+    EDV_CHECK((long long)s.h * s.w < (1ll << 31), "a frame beyond 2^31 pixels");
+    EDV_CHECK(s.mode == 0 || s.mode == 1, "mode: 0 depth, 1 disparity");
+    EDV_CHECK(s.mask_stride == 0 || s.mask_stride == (long long)s.h * s.w, "mask_stride: 0 (one mask for all frames) or h * w (a mask per frame)");
+    EDV_CHECK(aligned_to(s.x, 4), "depth not 4-byte aligned");
+    return 0;
+}
+
+inline int check_workspace(const CloudSel &s, const void *ws, size_t ws_bytes) {
+    EDV_CHECK(ws && aligned_to(ws, 8) && ws_bytes >= cloud_workspace(s.n, s.h, s.w, s.step), "workspace missing, too small or not 8-byte aligned (edv_cloud_workspace)");
+    return 0;
+}
+
+}  // namespace
+
+int cloud_tile_pixels() { return CLOUD_TILE; }
+
+size_t cloud_workspace(long long n, int h, int w, int step) {
+    if (n < 1 || n > 65535 || h < 1 || w < 1 || step < 1 || (long long)h * w >= (1ll << 31)) return 0;
+    return (size_t)(n * cloud_grid(h, w, step).tiles_per_frame) * sizeof(u64);
+}
+
+int cloud_count(const CloudSel &s, long long *offsets, void *ws, size_t ws_bytes, hipStream_t stream) {
+    EDV_TRY(check_selection(s));
+    EDV_CHECK(offsets && aligned_to(offsets, 8), "offsets missing or not 8-byte aligned");
+    EDV_TRY(check_workspace(s, ws, ws_bytes));
+    const CloudGrid g = cloud_grid(s.h, s.w, s.step);
+    const dim3 grid((unsigned)g.tiles_per_frame, (unsigned)s.n);
+    u64 *counts = static_cast<u64 *>(ws);
+    if (s.step == 1)
+        EDV_LAUNCH(cloud_count_kernel<true>, grid, dim3(CLOUD_THREADS), 0, stream, s, g.ow, g.pixels, counts);
+    else
+        EDV_LAUNCH(cloud_count_kernel<false>, grid, dim3(CLOUD_THREADS), 0, stream, s, g.ow, g.pixels, counts);
+    EDV_LAUNCH_OK();
+    EDV_LAUNCH(cloud_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, counts, s.n * g.tiles_per_frame, g.tiles_per_frame, offsets, s.n);
+    EDV_LAUNCH_OK();
+    return 0;
+}
+
+int cloud_scatter(const CloudSel &s, const double *cams, int cam_stride, const uint8_t *frames, const long long *offsets, const void *ws, size_t ws_bytes,
+                  float *points, uint8_t *colors, long long capacity, hipStream_t stream) {
+    EDV_TRY(check_selection(s));
+    EDV_CHECK(cams && aligned_to(cams, 8), "cameras missing or not 8-byte aligned");
+    EDV_CHECK(cam_stride == 0 || cam_stride == 21, "cam_stride: 0 (one camera for all frames) or 21 (a camera per frame)");
+    EDV_CHECK(offsets && aligned_to(offsets, 8), "offsets missing or not 8-byte aligned");
+    EDV_TRY(check_workspace(s, ws, ws_bytes));
+    EDV_CHECK(capacity >= 0, "negative capacity");
+    EDV_CHECK(points && aligned_to(points, 4), "points missing or not 4-byte aligned");
+    if (capacity == 0) return 0;
+    const CloudGrid g = cloud_grid(s.h, s.w, s.step);
+    EDV_LAUNCH(cloud_scatter_kernel, dim3((unsigned)g.tiles_per_frame, (unsigned)s.n), dim3(CLOUD_THREADS), 0, stream, s, g.ow, g.pixels, cams, cam_stride, frames,
+               offsets, static_cast<const u64 *>(ws), points, colors, (u64)capacity);
+    EDV_LAUNCH_OK();
+    return 0;
+}
+
+}  // namespace edv

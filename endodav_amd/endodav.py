@@ -829,6 +829,23 @@ class endodav(nn.Module):
 
         return _impl(self, frames, input_size=input_size, device=device, shard_windows=shard_windows, stitch=stitch, output=output, render=render)
 
+    def video_point_cloud(self, frames, spec, input_size=518, device="cuda", output="host"):
+        """A video as one coloured point cloud (not in the reference, which lifts depth read back from ``.npy`` files in numpy):
+        ``infer_video_depth(frames, stitch="device", output="device")`` followed by ``cloud.lift`` with ``spec`` (a ``cloud.Cloud``) and the
+        uint8 frames, uploaded once, as the colours.  The float32 video never reaches the host; only the kept points do, already compacted.
+        Returns a ``cloud.PointCloud``: numpy arrays, or with ``output="device"`` tensors on the GPU."""
+        from . import cloud
+
+        if not isinstance(spec, cloud.Cloud):
+            raise ValueError(f"spec must be a cloud.Cloud, got {type(spec).__name__}")
+        if output not in ("host", "device"):
+            raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+        frames = np.ascontiguousarray(frames)
+        depth = self.infer_video_depth(frames, input_size=input_size, device=device, stitch="device", output="device")
+        with torch.cuda.device(depth.device):
+            rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
+            return cloud.lift(depth, spec, frames=rgb, output=output)
+
     def stream_video_depth(self, frame_shape, device="cuda", output="host", render=None):
         """``infer_video_depth(stitch="device")`` for a live feed (not in the reference): returns a ``video.DepthStream`` whose
         ``push(chunk)`` takes uint8 frames [m, H, W, 3] as they arrive and returns the float32 depth [r, H, W] of the frames that became

@@ -334,6 +334,52 @@ int edv_render_range(const float *x_dev, int64_t n, int32_t h, int32_t w, int32_
 int edv_render_colorize(const float *x_dev, int64_t n, int32_t h, int32_t w, const float *range_dev, int32_t range_stride, float eps, int32_t clip,
                         const uint8_t *lut_dev, const uint8_t *beside_dev, uint8_t *out_dev, void *stream);
 
+/* ---- point clouds on the device (cloud.lift, model.video_point_cloud; the float64 numpy of get_point_cloud in the loaders
+ * of tools/viser-rgbd/utils and of visualize_reconstruction.py) ----
+ * Additive entry points: the ABI version stays as it is (the rule stated at edv_ingest_u8).  A clip of depth becomes world-space points with
+ * the frames' colours, masked, subsampled and compacted in order: frame-major, then row-major over the kept output pixels of a frame.
+ * edv_cloud_selection says which pixels are kept and at what depth; both calls take the same one.
+ *   x_dev [n, h, w] fp32, 1 <= n <= 65535, h*w < 2^31; mask_dev uint8 or NULL, [h, w] (mask_stride 0) or [n, h, w] (mask_stride h*w), non-zero = keep.
+ *   Output grid oh = ceil(h/step), ow = ceil(w/step).  Output pixel (oy, ox) samples source pixel sy = min(oy*step + step/2, h-1),
+ *   sx = min(ox*step + step/2, w-1) (integer division): the pixel that holds the grid position ((ox+0.5)*step, (oy+0.5)*step).  Depth, mask
+ *   and colour all come from that pixel.
+ *   Depth in fp32, every operation rounded separately, IEEE division:
+ *     mode 0 "depth":      z = x * gain
+ *     mode 1 "disparity":  scaled = lo + span * x;  z = 1.0f / scaled;  z = z * gain      (disp_to_depth, then a scale)
+ *   kept = (mask_dev == NULL || mask != 0) && z > near_z && z < far_z.  NaN fails both comparisons and +Inf fails z < far_z even for
+ *   far_z = +Inf, so every point is finite whenever the cameras are.
+ * cams_dev: 21 doubles per camera, Kinv[3][3], R[3][3], t[3], the matrices row-major; cam_stride 0: one camera for all frames, 21: one per frame.
+ *   Geometry in fp64, every multiply and add rounded separately, in this order:
+ *     u = (ox + 0.5) * step;  v = (oy + 0.5) * step
+ *     l_i = (Kinv[i][0]*u + Kinv[i][1]*v) + Kinv[i][2]
+ *     r_i = (R[i][0]*l_0 + R[i][1]*l_1) + R[i][2]*l_2
+ *     p_i = (float)(t_i + r_i * (double)z)
+ * edv_cloud_tile_pixels(): the output pixels one workgroup handles.  edv_cloud_workspace: 8 bytes per tile, n * ceil(oh*ow / tile) tiles, 8-byte
+ *   aligned device memory; 0 for a shape the calls refuse.  It grows with n, so a whole video is one call.
+ * edv_cloud_count (two launches): per-tile counts by wave ballot and popcount, the frame on blockIdx.y; then one workgroup scans them, 64-bit
+ *   and exclusive, over all tiles in frame-major order, in place in the workspace, and fills offsets_dev [n+1] int64: offsets[f] = the points of
+ *   the frames before f, offsets[n] = the total.  Reads 4 bytes (5 with a mask) per sampled pixel and nothing else.
+ * edv_cloud_scatter (one launch; the workspace and offsets_dev as edv_cloud_count left them for the same selection): recomputes the predicate,
+ *   ranks every kept pixel inside its tile, and writes point g = tile offset + rank only when g < capacity: points_dev [capacity][3] fp32 and,
+ *   when frames_dev [n, h, w, 3] uint8 and colors_dev are both non-NULL, colors_dev [capacity][3] uint8.  Every store is one float or one byte
+ *   of one point: never a byte outside capacity*12 or capacity*3, and never two workgroups in one dword.  capacity 0 launches nothing.
+ * No atomics and no waiting between workgroups: the same input gives the same bits on every call.
+ * Null required pointers, n outside 1..65535, h, w or step < 1, h*w >= 2^31, an unknown mode, cam_stride or mask_stride, a workspace that is
+ * missing, short or not 8-byte aligned, and capacity < 0 return non-zero and launch nothing. */
+typedef struct edv_cloud_selection {
+    const float *x_dev;
+    int64_t n;
+    int32_t h, w, step, mode;
+    float lo, span, gain, near_z, far_z;
+    const uint8_t *mask_dev;
+    int64_t mask_stride;
+} edv_cloud_selection;
+int32_t edv_cloud_tile_pixels(void);
+size_t edv_cloud_workspace(int64_t n, int32_t h, int32_t w, int32_t step);
+int edv_cloud_count(const edv_cloud_selection *sel, int64_t *offsets_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int edv_cloud_scatter(const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, const uint8_t *frames_dev, const int64_t *offsets_dev,
+                      const void *workspace_dev, size_t workspace_bytes, float *points_dev, uint8_t *colors_dev, int64_t capacity, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
