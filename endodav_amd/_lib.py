@@ -145,6 +145,12 @@ SIGNATURES = {
     "edv_cloud_workspace": (C.c_size_t, [_i64, _i32, _i32, _i32]),
     "edv_cloud_count": (C.c_int, [C.c_void_p, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_cloud_scatter": (C.c_int, [C.c_void_p, _fp, _i32, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _i64, C.c_void_p]),
+    # surface fusion on the device (additive, ABI stays 15): a TsdfVolume, and for integrate the cloud's CloudSelection
+    "edv_tsdf_integrate": (C.c_int, [C.c_void_p, C.c_void_p, _fp, _i32, _fp, C.c_void_p]),
+    "edv_tsdf_tile_voxels": (_i32, []),
+    "edv_tsdf_workspace": (C.c_size_t, [_i32, _i32, _i32]),
+    "edv_tsdf_count": (C.c_int, [C.c_void_p, _f32, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_tsdf_extract": (C.c_int, [C.c_void_p, _f32, _fp, C.c_size_t, _fp, _fp, _i64, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),
@@ -242,6 +248,12 @@ class CloudSelection(C.Structure):
     """edv_cloud_selection (include/endodav_hip.h): which pixels of a clip are kept and at what depth."""
     _fields_ = [("x_dev", C.c_void_p), ("n", _i64), ("h", _i32), ("w", _i32), ("step", _i32), ("mode", _i32), ("lo", _f32), ("span", _f32), ("gain", _f32),
                 ("near_z", _f32), ("far_z", _f32), ("mask_dev", C.c_void_p), ("mask_stride", _i64)]
+
+
+class TsdfVolume(C.Structure):
+    """edv_tsdf_volume (include/endodav_hip.h): the device arrays and the geometry of a TSDF volume."""
+    _fields_ = [("tsdf_dev", C.c_void_p), ("weight_dev", C.c_void_p), ("color_dev", C.c_void_p), ("nx", _i32), ("ny", _i32), ("nz", _i32),
+                ("origin", _f64 * 3), ("voxel", _f64), ("trunc", _f64), ("max_weight", _f32)]
 
 
 class GemmDescC(C.Structure):

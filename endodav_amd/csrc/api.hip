@@ -307,6 +307,29 @@ int edv_cloud_scatter(const edv_cloud_selection *sel, const double *cams_dev, in
                          points_dev, colors_dev, capacity, (hipStream_t)stream);
 }
 
+namespace {
+TsdfVol tsdf_vol(const edv_tsdf_volume &v) {
+    return TsdfVol{v.tsdf_dev, v.weight_dev, v.color_dev, v.nx, v.ny, v.nz, {v.origin[0], v.origin[1], v.origin[2]}, v.voxel, v.trunc, v.max_weight};
+}
+}  // namespace
+int32_t edv_tsdf_tile_voxels(void) { return tsdf_tile_voxels(); }
+size_t edv_tsdf_workspace(int32_t nx, int32_t ny, int32_t nz) { return tsdf_workspace(nx, ny, nz); }
+int edv_tsdf_integrate(const edv_tsdf_volume *vol, const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, const uint8_t *frames_dev,
+                       void *stream) {
+    EDV_CHECK(vol, "null volume");
+    EDV_CHECK(sel, "null selection");
+    return tsdf_integrate(tsdf_vol(*vol), cloud_sel(*sel), cams_dev, cam_stride, frames_dev, (hipStream_t)stream);
+}
+int edv_tsdf_count(const edv_tsdf_volume *vol, float min_weight, int64_t *total_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    EDV_CHECK(vol, "null volume");
+    return tsdf_count(tsdf_vol(*vol), min_weight, reinterpret_cast<long long *>(total_dev), workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+int edv_tsdf_extract(const edv_tsdf_volume *vol, float min_weight, const void *workspace_dev, size_t workspace_bytes, float *points_dev, uint8_t *colors_dev,
+                     int64_t capacity, void *stream) {
+    EDV_CHECK(vol, "null volume");
+    return tsdf_extract(tsdf_vol(*vol), min_weight, workspace_dev, workspace_bytes, points_dev, colors_dev, capacity, (hipStream_t)stream);
+}
+
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream) {

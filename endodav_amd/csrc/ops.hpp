@@ -167,6 +167,19 @@ size_t cloud_workspace(long long n, int h, int w, int step);  // bytes; 0 for a 
 int cloud_count(const CloudSel &s, long long *offsets, void *ws, size_t ws_bytes, hipStream_t stream);
 int cloud_scatter(const CloudSel &s, const double *cams, int cam_stride, const uint8_t *frames, const long long *offsets, const void *ws, size_t ws_bytes,
                   float *points, uint8_t *colors, long long capacity, hipStream_t stream);
+// surface fusion on the device (tsdf.hip): a truncated signed distance volume [nz, ny, nx] (edv_tsdf_volume) that tsdf_integrate folds a clip
+// into through cams [1 or n][18] doubles, one thread per voxel; tsdf_count / tsdf_extract compact its zero crossings in order
+struct TsdfVol {
+    float *tsdf, *weight, *color;  // color [nz, ny, nx, 3] or null
+    int nx, ny, nz;
+    double origin[3], voxel, trunc;
+    float max_weight;
+};
+int tsdf_tile_voxels();  // voxels per workgroup of the extract kernels, 8 workspace bytes each
+size_t tsdf_workspace(int nx, int ny, int nz);  // bytes; 0 for a shape the calls refuse
+int tsdf_integrate(const TsdfVol &v, const CloudSel &s, const double *cams, int cam_stride, const uint8_t *frames, hipStream_t stream);
+int tsdf_count(const TsdfVol &v, float min_weight, long long *total, void *ws, size_t ws_bytes, hipStream_t stream);
+int tsdf_extract(const TsdfVol &v, float min_weight, const void *ws, size_t ws_bytes, float *points, uint8_t *colors, long long capacity, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -846,6 +846,29 @@ class endodav(nn.Module):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             return cloud.lift(depth, spec, frames=rgb, output=output)
 
+    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host"):
+        """A video as one coloured surface (not in the reference): ``infer_video_depth(frames, stitch="device", output="device")``, then every
+        frame integrated into the TSDF ``volume`` (a ``fusion.Volume``) with ``spec`` (a ``cloud.Cloud`` with ``step=1``: intrinsics, poses,
+        depth rule and mask) and the uint8 frames, uploaded once, as the colours, then the zero crossings of the volume between voxels of
+        weight >= ``min_weight`` (``fusion.Tsdf``).  The float32 video never reaches the host; only the surface points do.
+        Returns a ``cloud.PointCloud`` with ``offsets = [0, total]``: numpy arrays, or with ``output="device"`` tensors on the GPU."""
+        from . import cloud, fusion
+
+        if not isinstance(spec, cloud.Cloud):
+            raise ValueError(f"spec must be a cloud.Cloud, got {type(spec).__name__}")
+        if not isinstance(volume, fusion.Volume):
+            raise ValueError(f"volume must be a fusion.Volume, got {type(volume).__name__}")
+        if int(spec.step) != 1:  # refused before the video is inferred, not after
+            raise ValueError(f"fusion samples the full-resolution clip: the Cloud must have step 1, got {spec.step}")
+        fusion._check_surface(min_weight, output)
+        frames = np.ascontiguousarray(frames)
+        depth = self.infer_video_depth(frames, input_size=input_size, device=device, stitch="device", output="device")
+        with torch.cuda.device(depth.device):
+            rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
+            tsdf = fusion.Tsdf(volume, coloured=True, device=depth.device)
+            tsdf.integrate(depth, spec, frames=rgb)
+            return tsdf.surface(min_weight=min_weight, output=output)
+
     def stream_video_depth(self, frame_shape, device="cuda", output="host", render=None):
         """``infer_video_depth(stitch="device")`` for a live feed (not in the reference): returns a ``video.DepthStream`` whose
         ``push(chunk)`` takes uint8 frames [m, H, W, 3] as they arrive and returns the float32 depth [r, H, W] of the frames that became

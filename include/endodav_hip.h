@@ -380,6 +380,56 @@ int edv_cloud_count(const edv_cloud_selection *sel, int64_t *offsets_dev, void *
 int edv_cloud_scatter(const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, const uint8_t *frames_dev, const int64_t *offsets_dev,
                       const void *workspace_dev, size_t workspace_bytes, float *points_dev, uint8_t *colors_dev, int64_t capacity, void *stream);
 
+/* ---- surface fusion on the device (fusion.Tsdf, model.video_surface; not in the reference, whose 3d_reconstruction clouds concatenate the frames) ----
+ * Additive entry points: the ABI version stays as it is (the rule stated at edv_ingest_u8).  A clip of depth with its cameras is folded into one
+ * truncated signed distance (TSDF) volume, and the zero crossings of the volume come out as an ordered, compacted point list.
+ * edv_tsdf_volume: nx * ny * nz voxels, x fastest, nx*ny*nz < 2^31.  tsdf_dev and weight_dev [nz, ny, nx] fp32, color_dev [nz, ny, nx, 3] fp32 or
+ *   NULL.  A fresh volume is tsdf = 1, weight = 0, color = 0.  Voxel (i_x, i_y, i_z) has its centre at c_a = origin[a] + (i_a + 0.5) * voxel, fp64.
+ * edv_tsdf_integrate (one launch for the whole clip): one thread owns one voxel, loads it once, takes the n frames of the selection in order with
+ *   the voxel in registers, and stores it once, only if some frame updated it.  The selection is the cloud's, with step == 1; frames_dev
+ *   [n, h, w, 3] uint8 goes with a coloured volume and NULL with an uncoloured one.
+ *   cams_dev: 18 doubles per camera, W[3][4] = rows 0..2 of inv(T_world_camera), row-major, then K00 K01 K02 K10 K11 K12 (the last row of K is
+ *   0 0 1); cam_stride 0: one camera for all frames, 18: one per frame.  Per frame, every multiply, add and divide rounded on its own:
+ *     fp64  q_i = ((W[i][0]*c_x + W[i][1]*c_y) + W[i][2]*c_z) + W[i][3];   skip the frame unless q_2 > 0 (which also skips NaN)
+ *     fp64  u = ((K00*q_0 + K01*q_1) + K02*q_2) / q_2;  v = ((K10*q_0 + K11*q_1) + K12*q_2) / q_2       (pixel centres at (x + 0.5, y + 0.5))
+ *           skip unless u >= 0 && u < w && v >= 0 && v < h, tested in fp64 before any conversion;  px = (int)u, py = (int)v
+ *     fp32  z and kept of pixel (py, px) exactly as in the selection above (depth or disparity rule, gain, mask, near_z < z < far_z,
+ *           non-finite dropped);  skip the frame if the pixel is not kept
+ *     fp64  sdf = (double)z - q_2;  skip if sdf < -trunc;  r = sdf / trunc;  d = (float)(r < 1 ? r : 1)
+ *     fp32  wn = weight + 1;  tsdf = (tsdf * weight + d) / wn;  per channel color = (color * weight + (float)rgb) / wn;
+ *           weight = wn < max_weight ? wn : max_weight
+ * Extraction has the cloud's three steps.  Voxel a runs in linear order, axis k runs x, y, z, b = a + e_k is the neighbour along that axis and
+ *   must lie inside the grid.  The pair emits a point when weight_a >= min_weight && weight_b >= min_weight && (tsdf_a < 0) != (tsdf_b < 0);
+ *   0 and -0 count as non-negative.  Points are ordered voxel-major, axis-minor.
+ *     fp32  t = tsdf_a / (tsdf_a - tsdf_b)                        (the signs differ, so the divisor is never zero)
+ *     fp64  p_k = origin[k] + ((i_k + 0.5) + (double)t) * voxel;  the other two coordinates are the voxel centre's;  stored as float
+ *     fp32  per channel c = c_a + t * (c_b - c_a);  colour = (uint8) min(255, max(0, floor(c + 0.5)))
+ * edv_tsdf_tile_voxels(): the voxels one workgroup of the extraction handles.  edv_tsdf_workspace: 8 bytes per tile, ceil(nx*ny*nz / tile) tiles,
+ *   8-byte aligned device memory; 0 for a shape the calls refuse.
+ * edv_tsdf_count (two launches): per-tile counts by wave ballot and popcount, then one workgroup scans them, 64-bit and exclusive, in place in
+ *   the workspace, and writes the number of points to total_dev[0].
+ * edv_tsdf_extract (one launch; the workspace as edv_tsdf_count left it for the same volume and min_weight): recomputes the predicates, ranks
+ *   every crossing inside its tile and writes point g = tile offset + rank only when g < capacity: points_dev [capacity][3] fp32 and, when
+ *   colors_dev is not NULL (the volume must then be coloured), colors_dev [capacity][3] uint8.  Every store is one float or one byte of one
+ *   point: never a byte outside capacity*12 or capacity*3, never two workgroups in one dword.  capacity 0 launches nothing.
+ * No atomics and no waiting between workgroups: the same input gives the same bits on every call.
+ * A null required pointer, a dimension below 1, nx*ny*nz >= 2^31, a voxel, trunc or max_weight that is not finite and positive, a selection the
+ * cloud refuses or with step != 1, a cam_stride other than 0 or 18, frames given to a volume without colour or a coloured volume integrated
+ * without frames, a workspace that is missing, short or not 8-byte aligned, and capacity < 0 return non-zero and launch nothing. */
+typedef struct edv_tsdf_volume {
+    float *tsdf_dev, *weight_dev, *color_dev;
+    int32_t nx, ny, nz;
+    double origin[3], voxel, trunc;
+    float max_weight;
+} edv_tsdf_volume;
+int edv_tsdf_integrate(const edv_tsdf_volume *vol, const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, const uint8_t *frames_dev,
+                       void *stream);
+int32_t edv_tsdf_tile_voxels(void);
+size_t edv_tsdf_workspace(int32_t nx, int32_t ny, int32_t nz);
+int edv_tsdf_count(const edv_tsdf_volume *vol, float min_weight, int64_t *total_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int edv_tsdf_extract(const edv_tsdf_volume *vol, float min_weight, const void *workspace_dev, size_t workspace_bytes, float *points_dev, uint8_t *colors_dev,
+                     int64_t capacity, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
