@@ -151,6 +151,10 @@ SIGNATURES = {
     "edv_tsdf_workspace": (C.c_size_t, [_i32, _i32, _i32]),
     "edv_tsdf_count": (C.c_int, [C.c_void_p, _f32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_tsdf_extract": (C.c_int, [C.c_void_p, _f32, _fp, C.c_size_t, _fp, _fp, _i64, C.c_void_p]),
+    # triangle meshes from the volume (additive, ABI stays 15)
+    "edv_tsdf_mesh_workspace": (C.c_size_t, [_i32, _i32, _i32]),
+    "edv_tsdf_mesh_count": (C.c_int, [C.c_void_p, _f32, _fp, _fp, C.c_size_t, C.c_void_p]),
+    "edv_tsdf_mesh_extract": (C.c_int, [C.c_void_p, _f32, _fp, C.c_size_t, _fp, _fp, _fp, _i64, _fp, _i64, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

@@ -330,6 +330,19 @@ int edv_tsdf_extract(const edv_tsdf_volume *vol, float min_weight, const void *w
     return tsdf_extract(tsdf_vol(*vol), min_weight, workspace_dev, workspace_bytes, points_dev, colors_dev, capacity, (hipStream_t)stream);
 }
 
+size_t edv_tsdf_mesh_workspace(int32_t nx, int32_t ny, int32_t nz) { return tsdf_mesh_workspace(nx, ny, nz); }
+int edv_tsdf_mesh_count(const edv_tsdf_volume *vol, float min_weight, int64_t *totals_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    EDV_CHECK(vol, "null volume");
+    return tsdf_mesh_count(tsdf_vol(*vol), min_weight, reinterpret_cast<long long *>(totals_dev), workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+// min_weight is not read again: the flags edv_tsdf_mesh_count left in the workspace hold every comparison with it
+int edv_tsdf_mesh_extract(const edv_tsdf_volume *vol, float /*min_weight*/, const void *workspace_dev, size_t workspace_bytes, float *vertices_dev,
+                          float *normals_dev, uint8_t *colors_dev, int64_t vertex_capacity, int32_t *triangles_dev, int64_t triangle_capacity, void *stream) {
+    EDV_CHECK(vol, "null volume");
+    return tsdf_mesh_extract(tsdf_vol(*vol), workspace_dev, workspace_bytes, vertices_dev, normals_dev, colors_dev, vertex_capacity, triangles_dev,
+                             triangle_capacity, (hipStream_t)stream);
+}
+
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream) {

@@ -180,6 +180,13 @@ size_t tsdf_workspace(int nx, int ny, int nz);  // bytes; 0 for a shape the call
 int tsdf_integrate(const TsdfVol &v, const CloudSel &s, const double *cams, int cam_stride, const uint8_t *frames, hipStream_t stream);
 int tsdf_count(const TsdfVol &v, float min_weight, long long *total, void *ws, size_t ws_bytes, hipStream_t stream);
 int tsdf_extract(const TsdfVol &v, float min_weight, const void *ws, size_t ws_bytes, float *points, uint8_t *colors, long long capacity, hipStream_t stream);
+// triangle meshes from the volume (tsdf_mesh.hip): marching tetrahedra on the Kuhn split of every cell whose eight corners are observed.
+// tsdf_mesh_count fills the workspace (flags, vertex masks, vertex bases, tile offsets) and leaves totals[0] = vertices, totals[1] = triangles;
+// tsdf_mesh_extract reads it and writes the first vertex_capacity vertices and the first triangle_capacity triangles
+size_t tsdf_mesh_workspace(int nx, int ny, int nz);  // bytes: 6 per voxel and 16 per tile; 0 for a shape the calls refuse
+int tsdf_mesh_count(const TsdfVol &v, float min_weight, long long *totals, void *ws, size_t ws_bytes, hipStream_t stream);
+int tsdf_mesh_extract(const TsdfVol &v, const void *ws, size_t ws_bytes, float *vertices, float *normals, uint8_t *colors, long long vertex_capacity,
+                      int *triangles, long long triangle_capacity, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

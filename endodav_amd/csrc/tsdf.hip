@@ -18,18 +18,10 @@
 #include "ops.hpp"
 
 #include "cloud_common.hpp"  // depth_value, kept, cloud_scan_kernel, check_selection: shared with pointcloud.hip
+#include "tsdf_common.hpp"   // TSDF_TILE, voxel_index, tiles_of, check_volume: shared with tsdf_mesh.hip
 
 namespace edv {
 namespace {
-
-constexpr int TSDF_THREADS = 256, TSDF_WAVES = TSDF_THREADS / WAVE;
-constexpr int TSDF_ITERS = 4;
-constexpr int TSDF_TILE = TSDF_THREADS * TSDF_ITERS;  // voxels per workgroup of count and extract: the one constant behind tsdf_tile_voxels()
-
-__device__ __forceinline__ void voxel_index(const TsdfVol &v, unsigned a, unsigned &ix, unsigned &iy, unsigned &iz) {
-    const unsigned r = a / (unsigned)v.nx;
-    ix = a - r * (unsigned)v.nx, iz = r / (unsigned)v.ny, iy = r - iz * (unsigned)v.ny;
-}
 
 // grid: ceil(voxels / TSDF_THREADS).  cam = W[3][4] (rows 0..2 of inv(T_world_camera)), then K00 K01 K02 K10 K11 K12
 template <bool COLOUR>
@@ -203,21 +195,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_extract_kernel(TsdfVol v, f
     }
 }
 
-inline long long tiles_of(long long voxels) { return (voxels + TSDF_TILE - 1) / TSDF_TILE; }
-
-inline bool positive(double x) { return std::isfinite(x) && x > 0.0; }
-
-// the volume's own fields; `voxels` = nx * ny * nz < 2^31
-inline int check_volume(const TsdfVol &v, long long &voxels) {
-    EDV_CHECK(v.tsdf && v.weight, "null tsdf or weight");
-    EDV_CHECK(aligned_to(v.tsdf, 4) && aligned_to(v.weight, 4) && aligned_to(v.color, 4), "volume arrays not 4-byte aligned");
-    EDV_CHECK(v.nx >= 1 && v.ny >= 1 && v.nz >= 1, "nx, ny and nz must be at least 1");
-    EDV_CHECK((long long)v.nx * v.ny < (1ll << 31) && (long long)v.nx * v.ny * v.nz < (1ll << 31), "a volume of 2^31 voxels or more");
-    EDV_CHECK(positive(v.voxel) && positive(v.trunc) && positive((double)v.max_weight), "voxel, trunc and max_weight must be finite and positive");
-    voxels = (long long)v.nx * v.ny * v.nz;
-    return 0;
-}
-
 inline int check_workspace(const TsdfVol &v, const void *ws, size_t ws_bytes) {
     EDV_CHECK(ws && aligned_to(ws, 8) && ws_bytes >= tsdf_workspace(v.nx, v.ny, v.nz), "workspace missing, too small or not 8-byte aligned (edv_tsdf_workspace)");
     return 0;
@@ -228,7 +205,7 @@ inline int check_workspace(const TsdfVol &v, const void *ws, size_t ws_bytes) {
 int tsdf_tile_voxels() { return TSDF_TILE; }
 
 size_t tsdf_workspace(int nx, int ny, int nz) {
-    if (nx < 1 || ny < 1 || nz < 1 || (long long)nx * ny >= (1ll << 31) || (long long)nx * ny * nz >= (1ll << 31)) return 0;
+    if (!volume_dims_ok(nx, ny, nz)) return 0;
     return (size_t)tiles_of((long long)nx * ny * nz) * sizeof(u64);
 }
 

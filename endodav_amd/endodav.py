@@ -846,14 +846,17 @@ class endodav(nn.Module):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             return cloud.lift(depth, spec, frames=rgb, output=output)
 
-    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host"):
+    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host", surface="points"):
         """A video as one coloured surface (not in the reference): ``infer_video_depth(frames, stitch="device", output="device")``, then every
         frame integrated into the TSDF ``volume`` (a ``fusion.Volume``) with ``spec`` (a ``cloud.Cloud`` with ``step=1``: intrinsics, poses,
         depth rule and mask) and the uint8 frames, uploaded once, as the colours, then the zero crossings of the volume between voxels of
         weight >= ``min_weight`` (``fusion.Tsdf``).  The float32 video never reaches the host; only the surface points do.
-        Returns a ``cloud.PointCloud`` with ``offsets = [0, total]``: numpy arrays, or with ``output="device"`` tensors on the GPU."""
+        Returns a ``cloud.PointCloud`` with ``offsets = [0, total]``: numpy arrays, or with ``output="device"`` tensors on the GPU.
+        ``surface="mesh"`` returns the triangle mesh of the volume instead, a ``fusion.Mesh`` with normals and colours (``fusion.Tsdf.mesh``)."""
         from . import cloud, fusion
 
+        if surface not in ("points", "mesh"):
+            raise ValueError(f"surface must be 'points' or 'mesh', got {surface!r}")
         if not isinstance(spec, cloud.Cloud):
             raise ValueError(f"spec must be a cloud.Cloud, got {type(spec).__name__}")
         if not isinstance(volume, fusion.Volume):
@@ -867,6 +870,8 @@ class endodav(nn.Module):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             tsdf = fusion.Tsdf(volume, coloured=True, device=depth.device)
             tsdf.integrate(depth, spec, frames=rgb)
+            if surface == "mesh":
+                return tsdf.mesh(min_weight=min_weight, output=output)
             return tsdf.surface(min_weight=min_weight, output=output)
 
     def stream_video_depth(self, frame_shape, device="cuda", output="host", render=None):

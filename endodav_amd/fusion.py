@@ -1,5 +1,5 @@
 """Surface fusion on the GPU (opt-in): a depth video with its poses integrated into one truncated signed distance (TSDF) volume, and the zero
-crossings of that volume as one coloured point list.  Not in the reference, whose ``3d_reconstruction`` clouds concatenate every frame's points:
+crossings of that volume as one coloured point list or as one coloured, oriented, indexed triangle mesh.  Not in the reference, whose ``3d_reconstruction`` clouds concatenate every frame's points:
 a thousand re-observations of the same tissue, each frame's depth noise a shell of its own.  Here every voxel averages what the frames saw.
 
 ``Volume`` says where the voxels are; ``Tsdf`` owns the arrays on the GPU (``edv_tsdf_integrate`` / ``edv_tsdf_count`` / ``edv_tsdf_extract``,
@@ -23,11 +23,42 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
             float32  c = c_a + t * (c_b - c_a);  colour = uint8(min(255, max(0, floor(c + 0.5))))
             ordered voxel-major, axis-minor
 
-What is not built: meshes and normals (the points are the edge crossings marching cubes would start from), hashed or sparse volumes, and pose
-estimation; poses are inputs, as for the cloud."""
+  mesh      marching tetrahedra on the Kuhn split of every cell (``Tsdf.mesh`` / ``TsdfHost.mesh`` -> ``Mesh``; ``edv_tsdf_mesh_count`` /
+            ``edv_tsdf_mesh_extract``).  Six tetrahedra around the body diagonal, the same in every cell, so neighbouring cells agree on the
+            diagonals of their shared faces: a 16-case rule with no ambiguous case and a watertight, consistently oriented mesh, at up to 12
+            triangles a cell.
+            corners   corner c in 0..7 of a cell has offset off(c) = (c&1, c>>1&1, c>>2&1) in (x, y, z), which is also its linear hop.  Voxel a is
+                      observed when weight[a] >= min_weight and inside when tsdf[a] < 0 (0 and -0 are outside, as for the surface).
+            cells     the cell of voxel a exists when i_x+1 < nx, i_y+1 < ny and i_z+1 < nz; it is valid when its eight corners are observed.
+                      Only valid cells emit triangles.
+            vertices  voxel a owns the seven edges a -> a + off(d), d = 1..7: three axis edges, three face diagonals, the body diagonal.  Edge
+                      (a, d) carries a vertex when b = a + off(d) is in the grid, a and b are observed, inside(a) != inside(b), and a valid
+                      cell contains the edge: the cell of a - off(s) for some s in 0..7 with s & d == 0 that lies in the grid.  Ordered
+                      voxel-major (x fastest), d-minor; every vertex is referenced by a triangle.
+            float32   t = tsdf_a / (tsdf_a - tsdf_b)
+            float64   p_k = origin_k + (d_k ? (i_k + 0.5) + float64(t) : (i_k + 0.5)) * voxel, stored as float32
+            float32   colour exactly the surface's: c = c_a + t * (c_b - c_a);  uint8(min(255, max(0, floor(c + 0.5))))
+            float32   normal, every operation rounded separately: the gradient of a voxel is g_k = tsdf[i_k -> min(i_k+1, n_k-1)] -
+                      tsdf[i_k -> max(i_k-1, 0)] (no division; unobserved voxels contribute their stored value, a fresh one 1);
+                      n_k = g_k(a) + t * (g_k(b) - g_k(a));  s = (n_x*n_x + n_y*n_y) + n_z*n_z;  len = sqrt(s), correctly rounded;
+                      n_k / len if len > 0, otherwise (0, 0, 0).  Normals point to the positive side, free space: the side the triangles face.
+            tetrahedra  for the permutations (p, q, r) of (0, 1, 2) in lexicographic order the corners (c0, c1, c2, c3) = (0, 1<<p,
+                      (1<<p)|(1<<q), 7); bit i of the case mask m is set when corner c_i is inside.
+            triangles  ins and outs the corner positions i, ascending.  m = 0 or 15: nothing.  One inside a: the polygon [(a, o) for o in outs];
+                      one outside o: [(i, o) for i in ins]; two inside a < b and two outside c < d: [(a, c), (a, d), (b, d), (b, c)].  With
+                      the polygon's points at the edge midpoints of the unit cube, the list is reversed if (P1-P0) x (P2-P0) . (mean of the
+                      outside corners - mean of the inside corners) < 0.  Emitted: (P0, P1, P2) and for a quad also (P0, P2, P3).  Polygon
+                      edge (i, j) is the cube edge between corners c_i and c_j: the smaller corner u is the owner's offset, d = v - u, and the
+                      triangle stores the index of that vertex.  Ordered cell-major (linear index of the cell's voxel), then tetrahedron,
+                      then the one or two triangles; int32.  ``MESH_TABLE`` holds the 6 x 16 rule, derived from this text at import.
+            Degenerate cases stay: tsdf_a == 0 gives t = 0, so several vertices coincide and some triangles have zero area; the topology is
+            unaffected and nothing is filtered.
+
+What is not built: hashed or sparse volumes, and pose estimation; poses are inputs, as for the cloud."""
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import math
 from dataclasses import dataclass
 
@@ -142,6 +173,56 @@ def _check_surface(min_weight, output):
     return np.float32(min_weight)
 
 
+@dataclass(eq=False)
+class Mesh:
+    """An indexed triangle mesh: numpy arrays, or tensors on the GPU."""
+    vertices: object                         # float32 [V, 3]
+    normals: object                          # float32 [V, 3] unit vectors towards free space, or None
+    colors: object                           # uint8 [V, 3], or None
+    triangles: object                        # int32 [F, 3] vertex indices, counter-clockwise seen from free space
+
+
+OFFSETS = tuple((d & 1, d >> 1 & 1, d >> 2 & 1) for d in range(8))
+TETRAHEDRA = tuple((0, 1 << p, (1 << p) | (1 << q), 7) for p, q, _ in itertools.permutations(range(3)))
+
+
+def _mesh_table() -> np.ndarray:
+    """int8 [6, 16, 2, 3, 2]: per tetrahedron and case mask up to two triangles of three edges (u, d), u the cube corner that owns the edge and
+    d = v - u; -1 where there is no triangle.  The rule of the module docstring, in integers: twice the midpoints, and the direction from the
+    inside to the outside corners scaled by both counts."""
+    table = np.full((6, 16, 2, 3, 2), -1, np.int8)
+    for ti, corners in enumerate(TETRAHEDRA):
+        P = np.array([OFFSETS[c] for c in corners], np.int64)
+        for m in range(1, 15):
+            ins, outs = [i for i in range(4) if m >> i & 1], [i for i in range(4) if not m >> i & 1]
+            if len(ins) == 1:
+                poly = [(ins[0], o) for o in outs]
+            elif len(ins) == 3:
+                poly = [(i, outs[0]) for i in ins]
+            else:
+                (a, b), (c, d) = ins, outs
+                poly = [(a, c), (a, d), (b, d), (b, c)]
+            pts = [P[i] + P[j] for i, j in poly]
+            towards = len(ins) * P[outs].sum(axis=0) - len(outs) * P[ins].sum(axis=0)
+            if np.cross(pts[1] - pts[0], pts[2] - pts[0]) @ towards < 0:
+                poly = poly[::-1]
+            for k, tri in enumerate([poly[:3]] if len(poly) == 3 else [poly[:3], [poly[0], poly[2], poly[3]]]):
+                for e, (i, j) in enumerate(tri):
+                    u, v = sorted((corners[i], corners[j]))
+                    table[ti, m, k, e] = (u, v - u)
+    return table
+
+
+MESH_TABLE = _mesh_table()
+MESH_TABLE.setflags(write=False)
+
+
+def _check_mesh(min_weight, normals, output):
+    if not isinstance(normals, (bool, np.bool_)):
+        raise ValueError(f"normals must be True or False, got {normals!r}")
+    return _check_surface(min_weight, output)
+
+
 def _staged(a: np.ndarray, dev: torch.device) -> torch.Tensor:
     """A host array on the GPU through pinned memory, ordered on the current stream: the host does not wait for the stream's earlier work."""
     a = np.ascontiguousarray(a)
@@ -246,6 +327,67 @@ class TsdfHost:
                 colors = np.minimum(np.float32(255.0), np.maximum(np.float32(0.0), np.floor(c + np.float32(0.5)))).astype(np.uint8)
         return PointCloud(points, colors, np.array([0, a.shape[0]], np.int64))
 
+    def mesh(self, min_weight: float = 1.0, normals: bool = True, output: str = "host") -> Mesh:
+        """The triangle mesh of the volume (module docstring, "mesh"), vectorised over the voxels."""
+        mw = _check_mesh(min_weight, normals, output)
+        if output != "host":
+            raise ValueError("the host mirror has no device output")
+        vol = self.volume
+        nx, ny, nz = vol.dims
+        origin, voxel = np.float64(vol.origin), np.float64(vol.voxel)
+        ix, iy, iz = idx = self._index()
+        t, wt = self.tsdf.reshape(-1), self.weight.reshape(-1)
+        N = vol.voxels
+        hop = np.array([dx + nx * (dy + ny * dz) for dx, dy, dz in OFFSETS], np.int64)
+        observed, inside = wt >= mw, t < 0
+        valid = np.zeros(N, bool)
+        cells = np.nonzero((ix + 1 < nx) & (iy + 1 < ny) & (iz + 1 < nz))[0]
+        valid[cells] = np.all([observed[cells + hop[c]] for c in range(8)], axis=0)
+        carries = np.zeros((N, 7), bool)                             # [a, d - 1]: edge (a, d) carries a vertex
+        for d in range(1, 8):
+            dx, dy, dz = OFFSETS[d]
+            a = np.nonzero((ix + dx < nx) & (iy + dy < ny) & (iz + dz < nz))[0]
+            used = np.zeros(a.shape[0], bool)
+            for s in range(8):
+                if s & d == 0:
+                    sx, sy, sz = OFFSETS[s]
+                    there = (ix[a] >= sx) & (iy[a] >= sy) & (iz[a] >= sz)
+                    used[there] |= valid[a[there] - hop[s]]
+            carries[a, d - 1] = observed[a] & observed[a + hop[d]] & (inside[a] != inside[a + hop[d]]) & used
+        rank = np.cumsum(carries, axis=1) - carries                   # vertices of the same voxel with a smaller d
+        owned = carries.sum(axis=1)
+        first = np.cumsum(owned) - owned                              # the index of a voxel's first vertex
+        a, k = np.nonzero(carries)                                    # row-major: voxel-major, d-minor
+        d = k + 1
+        b = a + hop[d]
+        with np.errstate(all="ignore"):
+            frac = t[a] / (t[a] - t[b])
+            vertices = np.empty((a.shape[0], 3), np.float32)
+            for j in range(3):
+                ctr = idx[j][a].astype(np.float64) + 0.5
+                vertices[:, j] = (origin[j] + np.where((d >> j) & 1 == 1, ctr + frac.astype(np.float64), ctr) * voxel).astype(np.float32)
+            unit = None
+            if normals:
+                g = np.stack([np.take(self.tsdf, np.minimum(np.arange(n) + 1, n - 1), axis=ax) - np.take(self.tsdf, np.maximum(np.arange(n) - 1, 0), axis=ax)
+                              for ax, n in ((2, nx), (1, ny), (0, nz))], axis=-1).reshape(-1, 3)
+                n = g[a] + frac[:, None] * (g[b] - g[a])
+                length = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+                unit = np.where((length > 0)[:, None], n / length[:, None], np.float32(0.0)).astype(np.float32)
+            colors = None
+            if self.color is not None:
+                col = self.color.reshape(-1, 3)
+                c = col[a] + frac[:, None] * (col[b] - col[a])
+                colors = np.minimum(np.float32(255.0), np.maximum(np.float32(0.0), np.floor(c + np.float32(0.5)))).astype(np.uint8)
+        cells = np.nonzero(valid)[0]
+        pattern = np.stack([inside[cells + hop[c]] for c in range(8)], axis=1)
+        case = np.stack([sum(pattern[:, c].astype(np.int64) << i for i, c in enumerate(corners)) for corners in TETRAHEDRA], axis=1)
+        edges = MESH_TABLE[np.arange(6)[None, :], case].astype(np.int64)      # [cells, 6, 2, 3, 2]
+        cell, ti, tri = np.nonzero(edges[..., 0, 0] >= 0)                     # row-major: cell-major, then tetrahedron, then triangle
+        u, dd = edges[cell, ti, tri, :, 0], edges[cell, ti, tri, :, 1]
+        w = cells[cell][:, None] + hop[u]
+        triangles = (first[w] + rank[w, dd - 1]).astype(np.int32).reshape(-1, 3)
+        return Mesh(vertices, unit, colors, triangles)
+
 
 class Tsdf:
     """A TSDF volume on the GPU.  ``integrate`` folds clips into it, ``surface`` reads its zero crossings; both run on the caller's current
@@ -340,3 +482,112 @@ class Tsdf:
                 host_c.copy_(colors, non_blocking=True)
             stream.synchronize()
             return PointCloud(host_p.numpy(), None if host_c is None else host_c.numpy(), offsets)
+
+    def mesh(self, min_weight: float = 1.0, normals: bool = True, output: str = "host") -> Mesh:
+        """The triangle mesh of the volume between voxels of weight >= ``min_weight`` (module docstring, "mesh"): the count, one read of the two
+        totals (the one host synchronisation), exact allocations, the extract.  Returns a ``Mesh`` of numpy arrays, or with ``output="device"``
+        of tensors on the GPU, ordered on the caller's stream.  ``normals=False`` leaves them out; ``colors`` is None for an uncoloured volume."""
+        mw = float(_check_mesh(min_weight, normals, output))
+        lib, dev, v = self._lib, self.device, self.volume
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            st = self._stream()
+            vol = self.struct()
+            ws = torch.empty(int(lib.edv_tsdf_mesh_workspace(*v.dims)), dtype=torch.uint8, device=dev)
+            totals_d = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(lib.edv_tsdf_mesh_count(C.byref(vol), mw, totals_d.data_ptr(), ws.data_ptr(), ws.numel(), st), "edv_tsdf_mesh_count")
+            totals_h = torch.empty(2, dtype=torch.int64, pin_memory=True)
+            totals_h.copy_(totals_d, non_blocking=True)
+            stream.synchronize()
+            nv, nt = int(totals_h[0]), int(totals_h[1])
+            if nv >= 2 ** 31:
+                raise ValueError(f"a mesh holds fewer than 2^31 vertices (its indices are int32), this one has {nv}")
+            shapes = [((nv, 3), torch.float32), ((nv, 3), torch.float32) if normals else None, ((nv, 3), torch.uint8) if self.coloured else None,
+                      ((nt, 3), torch.int32)]
+            out = [None if s is None else torch.empty(s[0], dtype=s[1], device=dev) for s in shapes]
+            if nv or nt:  # an empty mesh launches nothing
+                _lib.check(lib.edv_tsdf_mesh_extract(C.byref(vol), mw, ws.data_ptr(), ws.numel(), out[0].data_ptr(), _lib.ptr(out[1]), _lib.ptr(out[2]), nv,
+                                                     out[3].data_ptr(), nt, st), "edv_tsdf_mesh_extract")
+            if output == "device":
+                return Mesh(*out)
+            host = [None if o is None else torch.empty(o.shape, dtype=o.dtype, pin_memory=True) for o in out]
+            for h, o in zip(host, out):
+                if h is not None:
+                    h.copy_(o, non_blocking=True)
+            stream.synchronize()
+            return Mesh(*(None if h is None else h.numpy() for h in host))
+
+
+def _face_dtype():
+    return np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def _mesh_vertex_dtype(normals: bool, colours: bool):
+    fields = [(n, "<f4") for n in "xyz"] + ([(n, "<f4") for n in ("nx", "ny", "nz")] if normals else []) + ([(n, "u1") for n in ("red", "green", "blue")] if colours else [])
+    return np.dtype(fields)
+
+
+def _mesh_header(nv, nf, normals, colours):
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {nv}", "property float x", "property float y", "property float z"]
+    if normals:
+        header += ["property float nx", "property float ny", "property float nz"]
+    if colours:
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    return header + [f"element face {nf}", "property list uchar int vertex_indices", "end_header"]
+
+
+def write_mesh_ply(path, mesh: Mesh) -> None:
+    """Binary little-endian ``.ply``: vertices ``x y z`` float, then ``nx ny nz`` float and ``red green blue`` uchar where the mesh has them, and
+    faces as ``property list uchar int vertex_indices``.  Tensors on the GPU are copied to the host first."""
+    parts = [None if p is None else (p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)) for p in (mesh.vertices, mesh.normals, mesh.colors, mesh.triangles)]
+    vertices, normals, colors, triangles = parts
+    vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
+    vertex = np.empty(vertices.shape[0], _mesh_vertex_dtype(normals is not None, colors is not None))
+    columns = list(zip("xyz", vertices.T))
+    if normals is not None:
+        columns += list(zip(("nx", "ny", "nz"), np.asarray(normals, np.float32).reshape(-1, 3).T))
+    if colors is not None:
+        columns += list(zip(("red", "green", "blue"), np.asarray(colors, np.uint8).reshape(-1, 3).T))
+    for name, column in columns:
+        if column.shape[0] != vertex.shape[0]:
+            raise ValueError(f"{name}: {column.shape[0]} values for {vertex.shape[0]} vertices")
+        vertex[name] = column
+    triangles = np.asarray(triangles, np.int32).reshape(-1, 3)
+    face = np.empty(triangles.shape[0], _face_dtype())
+    face["n"], face["v"] = 3, triangles
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(_mesh_header(vertex.shape[0], face.shape[0], normals is not None, colors is not None)) + "\n").encode("ascii"))
+        fh.write(vertex.tobytes())
+        fh.write(face.tobytes())
+
+
+def read_mesh_ply(path) -> Mesh:
+    """A ``.ply`` as ``write_mesh_ply`` writes it -> ``Mesh`` of numpy arrays."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a .ply file")
+    lines = data[:end].decode("ascii").split("\n")[:-1] + ["end_header"]
+    try:
+        nv, nf = int(lines[2].split()[2]), int(next(ln for ln in lines if ln.startswith("element face ")).split()[2])
+    except (IndexError, ValueError, StopIteration):
+        raise ValueError(f"{path}: expected a binary little-endian .ply with vertices, then faces") from None
+    for normals, colours in itertools.product((False, True), repeat=2):
+        if lines == _mesh_header(nv, nf, normals, colours):
+            break
+    else:
+        raise ValueError(f"{path}: not a header write_mesh_ply writes")
+    vdt, fdt = _mesh_vertex_dtype(normals, colours), _face_dtype()
+    body = data[end + len(b"end_header\n"):]
+    if len(body) != nv * vdt.itemsize + nf * fdt.itemsize:
+        raise ValueError(f"{path}: {len(body)} bytes after the header, which says {nv} x {vdt.itemsize} + {nf} x {fdt.itemsize}")
+    vertex, face = np.frombuffer(body, vdt, nv), np.frombuffer(body, fdt, nf, offset=nv * vdt.itemsize)
+    if not (face["n"] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+
+    def columns(names, dtype):
+        return np.stack([vertex[n] for n in names], axis=1).astype(dtype) if nv else np.empty((0, 3), dtype)
+
+    return Mesh(columns("xyz", np.float32), columns(("nx", "ny", "nz"), np.float32) if normals else None,
+                columns(("red", "green", "blue"), np.uint8) if colours else None, face["v"].astype(np.int32).reshape(-1, 3))

@@ -430,6 +430,57 @@ int edv_tsdf_count(const edv_tsdf_volume *vol, float min_weight, int64_t *total_
 int edv_tsdf_extract(const edv_tsdf_volume *vol, float min_weight, const void *workspace_dev, size_t workspace_bytes, float *points_dev, uint8_t *colors_dev,
                      int64_t capacity, void *stream);
 
+/* ---- triangle meshes from the volume (fusion.Tsdf.mesh, model.video_surface(surface="mesh")) ----
+ * Additive entry points: the ABI version stays as it is.  Marching tetrahedra on the Kuhn split of every cell: six tetrahedra around the body
+ * diagonal, the same in every cell, so neighbouring cells agree on the diagonals of their shared faces.  A 16-case rule with no ambiguous case,
+ * a watertight and consistently oriented mesh, up to 12 triangles a cell.  The volume is only read.
+ * Corners and offsets: corner c in 0..7 of a cell has offset off(c) = (c & 1, c >> 1 & 1, c >> 2 & 1) in (x, y, z); off(d), d in 1..7, is also
+ *   the linear hop.  Voxel a is observed when weight[a] >= min_weight and inside when tsdf[a] < 0; 0 and -0 are outside, as for the points.
+ * Cells: the cell of voxel a exists when i_x + 1 < nx, i_y + 1 < ny and i_z + 1 < nz, and is valid when its eight corners are observed.  Only
+ *   valid cells emit triangles.
+ * Vertices: voxel a owns the seven edges a -> a + off(d), d = 1..7 (three axis edges, three face diagonals, the body diagonal).  Edge (a, d)
+ *   carries a vertex when b = a + off(d) is in the grid, a and b are observed, inside(a) != inside(b), and a valid cell contains the edge: the
+ *   cell of voxel a - off(s) for some s in 0..7 with (s & d) == 0 that lies in the grid.  Vertices are ordered voxel-major (x fastest), d-minor;
+ *   none is left unreferenced.
+ *     fp32  t = tsdf_a / (tsdf_a - tsdf_b)
+ *     fp64  p_k = origin[k] + (d_k ? (i_k + 0.5) + (double)t : (i_k + 0.5)) * voxel;  stored as float
+ *     fp32  per channel c = c_a + t * (c_b - c_a);  colour = (uint8) min(255, max(0, floor(c + 0.5)))          (exactly the points' colour)
+ *     fp32  normal, every operation rounded on its own: the gradient of a voxel is g_k = tsdf[i_k -> min(i_k + 1, n_k - 1)] -
+ *           tsdf[i_k -> max(i_k - 1, 0)], with no division (unobserved voxels contribute their stored value, a fresh one 1);
+ *           n_k = g_k(a) + t * (g_k(b) - g_k(a));  s = (n_x*n_x + n_y*n_y) + n_z*n_z;  len = sqrt(s), correctly rounded;
+ *           the normal is n_k / len if len > 0 and (0, 0, 0) otherwise.  It points to the positive side, free space, which the triangles face.
+ * Tetrahedra: for the permutations (p, q, r) of (0, 1, 2) in lexicographic order the corners (c0, c1, c2, c3) = (0, 1 << p,
+ *   (1 << p) | (1 << q), 7); bit i of the case mask m is set when corner c_i is inside.
+ * Triangles per case, ins and outs being the corner positions i in ascending order: m = 0 or 15 gives none; one inside a the polygon
+ *   [(a, o) for o in outs]; one outside o the polygon [(i, o) for i in ins]; two inside a < b and two outside c < d the polygon
+ *   [(a, c), (a, d), (b, d), (b, c)].  With the polygon's points at the edge midpoints of the unit cube, the list is reversed when
+ *   (P1 - P0) x (P2 - P0) . (mean of the outside corners - mean of the inside corners) < 0.  (P0, P1, P2) is emitted, and for a quad also
+ *   (P0, P2, P3).  Polygon edge (i, j) is the cube edge between corners c_i and c_j: the smaller corner u is the owner's offset, d = v - u, and
+ *   the triangle stores the index of that vertex.  Triangles are ordered cell-major (linear index of the cell's voxel), then tetrahedron, then
+ *   the one or two triangles; indices are int32.
+ * Degenerate cases stay as the rule gives them: tsdf_a == 0 gives t = 0, so several vertices coincide and some triangles have zero area; the
+ *   topology is unaffected and nothing is filtered.
+ * edv_tsdf_mesh_workspace: 16 bytes per tile of edv_tsdf_tile_voxels() voxels and 6 bytes per voxel, 8-byte aligned device memory; 0 for
+ *   dimensions the volume check refuses.
+ * edv_tsdf_mesh_count (five launches) fills the workspace: a flags byte per voxel (observed, inside, cell valid); from the flags the 7-bit mask
+ *   of the edges of a voxel that carry a vertex and the triangles of its cell, summed per tile by wave ballot and popcount; two 64-bit exclusive
+ *   scans; the u32 index of every voxel's first vertex.  totals_dev[0] is the number of vertices, totals_dev[1] the number of triangles.
+ * edv_tsdf_mesh_extract (up to two launches) takes the workspace as edv_tsdf_mesh_count left it for the same volume and min_weight and only
+ *   reads it (min_weight itself is not read again: the flags hold every comparison with it).  It writes vertex g only when
+ *   g < vertex_capacity: vertices_dev [vertex_capacity][3] fp32 and, where not NULL, normals_dev [vertex_capacity][3] fp32 and colors_dev
+ *   [vertex_capacity][3] uint8 (the volume must then be coloured); and triangle g only when g < triangle_capacity: triangles_dev
+ *   [triangle_capacity][3] int32.  Every store is one float, one byte or one int of one vertex or triangle.  A capacity of 0 launches nothing
+ *   for that output.  The caller compares totals_dev[0] with 2^31 before it extracts: a vertex_capacity of 2^31 or more is refused.
+ * No atomics and no waiting between workgroups: the same input gives the same bits on every call.
+ * A null volume, totals, vertices or triangles pointer, the volume refusals above, a workspace that is missing, short or not 8-byte aligned,
+ * outputs that are not 4-byte aligned, a negative capacity, a vertex capacity of 2^31 or more, and colours asked of a volume that has none
+ * return non-zero and launch nothing. */
+size_t edv_tsdf_mesh_workspace(int32_t nx, int32_t ny, int32_t nz);
+int edv_tsdf_mesh_count(const edv_tsdf_volume *vol, float min_weight, int64_t *totals_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int edv_tsdf_mesh_extract(const edv_tsdf_volume *vol, float min_weight, const void *workspace_dev, size_t workspace_bytes, float *vertices_dev,
+                          float *normals_dev, uint8_t *colors_dev, int64_t vertex_capacity, int32_t *triangles_dev, int64_t triangle_capacity,
+                          void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
