@@ -88,6 +88,12 @@ int edv_set_conv_impl(int32_t mode) {
     return 0;
 }
 
+int edv_set_x6_remainder(int32_t mode, int32_t cus) {
+    EDV_CHECK(mode >= 0 && mode <= 2 && cus >= 0, "edv_set_x6_remainder: mode 0 (off), 1 (by policy) or 2 (wherever supported); cus 0 = the device's count");
+    set_x6_remainder(mode, cus);
+    return 0;
+}
+
 int edv_conv3x3_dot(const float *x_dev, const float *wpacked_dev, const float *bias_dev, float *y_dev, int32_t F, int32_t H, int32_t W, int32_t Cin,
                     int32_t Cout, int32_t stride, int32_t pre_relu, int32_t post_relu, const float *w2_dev, const float *b2_dev, int32_t act2, void *stream) {
     EDV_CHECK(F > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "empty problem");
@@ -453,7 +459,26 @@ int edv_bilinear_add(const float *x_dev, const float *add_dev, float *y_dev, int
 
 // ---- test entry point (ABI 15): the launchers' planner and policies on a given slot count (tests/test_split_plan_cpu.py) ----
 int edv_split_plan(int32_t kind, int64_t tiles_or_tasks, int32_t slots, int32_t k_tiles, int64_t out[8]) {
-    EDV_CHECK(out && kind >= 0 && kind <= 3 && tiles_or_tasks > 0 && tiles_or_tasks < (1ll << 31) && k_tiles > 0, "kind 0..3, a positive count below 2^31");
+    if (kind == 5) {  // gemm_x6's remainder walk: the whole tile of raw block index `tiles_or_tasks` in a grid of `slots` workgroups, `k_tiles` of them run owners
+        EDV_CHECK(out && slots > 0 && k_tiles >= 0 && k_tiles <= slots && tiles_or_tasks >= k_tiles && tiles_or_tasks < slots, "kind 5: nsplit <= block < grid");
+        std::fill(out, out + 8, 0);
+        out[0] = front_whole_tile((int)tiles_or_tasks, slots, k_tiles);
+        return 0;
+    }
+    EDV_CHECK(out && kind >= 0 && kind <= 4 && tiles_or_tasks > 0 && tiles_or_tasks < (1ll << 31) && k_tiles > 0, "kind 0..5, a positive count below 2^31");
+    if (kind == 4) {  // gemm_x6's remainder plan: slots = CUs; on entry out[0] = resident workgroups per CU, out[1] = 1 (by policy) or 2 (wherever supported)
+        const int wgs = (int)out[0], mode = (int)out[1];
+        EDV_CHECK(slots > 0 && wgs > 0 && wgs <= 64 && (mode == 1 || mode == 2), "kind 4: out[0] = workgroups per CU, out[1] = mode 1 or 2");
+        const SplitPolicy &pol = gemm_x6_split_policy();
+        GemmSplit sp{};
+        long long grid;
+        plan_plain(tiles_or_tasks, pol, &sp, &grid);
+        const bool rem = gemm_x6_plan(tiles_or_tasks, k_tiles, slots * wgs, slots, wgs, mode, &sp, &grid) == 2;  // as launch_x6 decides
+        const int64_t r[8] = {1, grid, sp.first_split, sp.chunk, sp.nsplit, tiles_or_tasks - sp.first_split, sp.units, (int64_t)split_ws_floats(sp, pol)};
+        std::fill(out, out + 8, 0);  // another plan: all zero
+        if (rem) std::copy(r, r + 8, out);
+        return 0;
+    }
     if (kind == 3) {
         const TaskSplit t = plan_tasks(tiles_or_tasks, k_tiles, slots, false);
         const int64_t r[8] = {t.nsplit > 0, t.grid, t.whole_rounds, t.chunk, t.nsplit, t.leftover, t.units, (int64_t)t.pieces()};

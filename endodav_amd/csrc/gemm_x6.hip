@@ -40,7 +40,8 @@
 // Tile 128 x 128, 16 k per stage, 3 stages of 24 KB (two workgroups per CU), 4 waves each holding 64 x 64 (2 x 2 accumulators).  W DMA and the A loads run
 // two stages ahead.  LDS plane image: 32-byte rows, the two 16-byte halves of row r swapped when (r >> 3) & 1, so a 16-lane ds_read_b128 group covers all
 // 64 banks.  Work split: the stream-K scheme of streamk_plan.hpp / gemm_common.hpp (whole rounds of tiles, the leftover round cut along k into runs, the last arriver of a tile
-// merges the pieces in run order and applies the epilogue) with 128 x 128 pieces.
+// merges the pieces in run order and applies the epilogue) with 128 x 128 pieces; a shallow grid a few tiles past a whole number of rounds of CUs
+// splits only those tiles and starts their pieces first (plan_remainder), through the same hand-off.
 //
 // Used for the encoder's linears in inference (engine.hip: Run::linear picks it when the weight has planes and the context computes in
 // EDV_PRODUCTS_BF16X6); training keeps the fp32-MFMA kernels, whose saved activations the backward expects.
@@ -91,7 +92,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
     const int wm = wave >> 1, wn = wave & 1;
     const int tiles_n = (g.N + XBN - 1) / XBN, tiles_m = (int)((g.M + XBM - 1) / XBM);
     const int G = gridDim.x;
-    const int bid = xcd_remap(blockIdx.x, G);
+    // the remainder walk (streamk_plan.hpp: plan_remainder): the first nsplit raw block indices own one run each, every later one a whole tile
+    const bool front = SPLIT && sp.front != 0;
+    const int bid = front ? front_whole_tile(blockIdx.x, G, sp.nsplit) : xcd_remap(blockIdx.x, G);
     const int nkt = g.K / XBK;
     const __bf16 *Wp = reinterpret_cast<const __bf16 *>(g.Wx6);
     const auto rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16 *>(Wp), 0, 0xffffffff, 0x00020000);
@@ -106,15 +109,16 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const GemmDesc g, const
         fb[i] = 3 * XPLANE + rb * 32 + half_pos(rb, lh);
     }
 
-    const int tile_l0 = sp.whole_rounds * G;
-    const int run = split_run(sp, SPLIT, bid);
+    const int tile_l0 = front ? sp.first_split : sp.whole_rounds * G;
+    const int run = front ? ((int)blockIdx.x < sp.nsplit ? (int)blockIdx.x : -1) : split_run(sp, SPLIT, bid);
+    const int whole_rounds = front ? (run < 0 ? 1 : 0) : sp.whole_rounds;  // front: round 0 is tile `bid`
     long long u = split_run_begin(sp, run);
     const long long u_end = split_run_end(sp, run, u);
     int round = 0;
     for (;;) {
         int tile, kt0, kt1, lt = 0;
         float *part = nullptr;
-        if (round < sp.whole_rounds) {
+        if (round < whole_rounds) {
             tile = round * G + bid;
             kt0 = 0;
             kt1 = nkt;
@@ -381,6 +385,18 @@ int x6_slots() {
                                (const void *)gemm_x6_kernel<ACT, false>);
 }
 
+// process-wide switch of the remainder plan (edv_set_x6_remainder): mode 0 off, 1 by policy, 2 wherever supported; cus 0 = the device's count
+std::atomic<int> g_x6_rem_mode{1}, g_x6_rem_cus{0};
+
+int device_cus() {
+    static DeviceSlotCache cache;
+    return cache.get([] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        return cus;
+    });
+}
+
 template <int ACT>
 int launch_x6(const GemmDesc &d, long long tiles, hipStream_t st) {
     const SplitPolicy &pol = gemm_x6_split_policy();
@@ -391,7 +407,10 @@ int launch_x6(const GemmDesc &d, long long tiles, hipStream_t st) {
     plan_plain(tiles, pol, &sp, &grid);
     const int slots = x6_slots<ACT>();
     EDV_CHECK(slots > 0 && slots <= XMAX_COUNTERS, "occupancy query failed");
-    if (d.ws && !gemm_plain_forced() && plan_split(tiles, slots, d.K / XBK, pol, &sp, &grid)) {
+    const int dev_cus = device_cus(), set_cus = g_x6_rem_cus.load(std::memory_order_relaxed);
+    EDV_CHECK(dev_cus > 0, "device query failed");
+    if (d.ws && !gemm_plain_forced() &&
+        gemm_x6_plan(tiles, d.K / XBK, slots, set_cus > 0 && set_cus < dev_cus ? set_cus : dev_cus, slots / dev_cus, g_x6_rem_mode.load(std::memory_order_relaxed), &sp, &grid)) {
         split_bind(&sp, d.ws, pol);
         EDV_CHECK(split_ws_floats(sp, pol) <= d.ws_floats && (uintptr_t)d.ws % 16 == 0, "stream-K workspace too small (gemm_workspace)");
         EDV_LAUNCH((gemm_x6_kernel<ACT, true>), dim3((unsigned)grid), dim3(256), XNST * XSTAGE, st, d, sp);
@@ -412,6 +431,26 @@ const SplitPolicy &gemm_x6_split_policy() {
     static const SplitPolicy p{.min_kt = env_int("EDV_X6_SPLIT_MIN_KT", 48),  // k-steps per tile from which the split is used (A/B runs)
                                .min_tiles = 16, .max_rounds = 8, .widen = true, .counters = XMAX_COUNTERS, .slot_floats = XSLOT, .whole_rounds = true};
     return p;
+}
+
+// The remainder plan (streamk_plan.hpp): the constants and what they were measured against are in profiles/x6_remainder_notes.txt.
+// runs_per_cu: gemm_workspace() holds 16 pieces of 64 x 64 per CU = two runs' slot pairs of 128 x 128.
+const RemainderPolicy &gemm_x6_remainder_policy() {
+    static const RemainderPolicy p{.left_div = 16, .run_div = 6, .min_run = 3, .runs_per_cu = 2, .counters = XMAX_COUNTERS};
+    return p;
+}
+
+// Which plan a launch with a workspace takes: mode 2 takes the remainder plan wherever its walk is supported (tests, A/B runs); mode 1 where its
+// policy wants it, which comes before the stream-K plan: a grid that is resident at once has no whole round there, so that plan would cut EVERY
+// tile (ViT-S fc2 at T = 8, 258 tiles of 96 k-tiles: 91.3 -> 87.8 us).  Otherwise the stream-K plan where its policy wants it.
+int gemm_x6_plan(long long tiles, int nkt, int slots, int cus, int wgs_per_cu, int mode, GemmSplit *sp, long long *grid) {
+    if (mode != 0 && plan_remainder(tiles, nkt, cus, wgs_per_cu, mode == 2, gemm_x6_remainder_policy(), sp, grid)) return 2;
+    return plan_split(tiles, slots, nkt, gemm_x6_split_policy(), sp, grid) ? 1 : 0;
+}
+
+void set_x6_remainder(int mode, int cus) {
+    g_x6_rem_mode.store(mode < 0 || mode > 2 ? 1 : mode, std::memory_order_relaxed);
+    g_x6_rem_cus.store(cus > 0 ? cus : 0, std::memory_order_relaxed);
 }
 
 size_t gemm_x6_planes_bytes(int N, int K) { return (size_t)3 * N * K * 2; }

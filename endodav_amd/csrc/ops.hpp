@@ -94,6 +94,12 @@ bool conv_dot_enabled();  // conv_impl() != 1 and not EDV_CONV_DOT=0
 const SplitPolicy &gemm_dma_split_policy();
 const SplitPolicy &gemm_x6_split_policy();
 const SplitPolicy &conv_dma_split_policy();
+// gemm_x6's remainder plan (streamk_plan.hpp: plan_remainder) and its process-wide switch (edv_set_x6_remainder), read at every launch:
+// mode 0 off, 1 by policy (the default), 2 wherever the walk is supported; cus > 0 plans for that many CUs instead of the device's
+const RemainderPolicy &gemm_x6_remainder_policy();
+// the plan launch_x6 takes with a workspace (sp and grid start as plan_plain's): 0 plain, 1 stream-K (plan_split), 2 remainder (plan_remainder)
+int gemm_x6_plan(long long tiles, int nkt, int slots, int cus, int wgs_per_cu, int mode, GemmSplit *sp, long long *grid);
+void set_x6_remainder(int mode, int cus);
 // flops of the last-launched gemm tile choice, for the bench's roofline bookkeeping
 const char *gemm_kernel_name(const GemmDesc &d);
 

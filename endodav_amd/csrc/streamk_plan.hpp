@@ -23,6 +23,9 @@ struct GemmSplit {
     float *ws;   // piece slots (after the counters)
     int *cnt;    // one arrival counter per split tile
     int group_m = 1;  // gemm_x6.hip: row blocks per tile group of its tile order
+    // gemm_x6.hip, the remainder walk (plan_remainder below).  front != 0: the workgroups with raw block index < nsplit own run blockIdx.x and
+    // nothing else, every later one computes one whole tile (front_whole_tile), and the split tiles start at tile index first_split.
+    int front = 0, first_split = 0;
 };
 
 // Which launches of a kernel family take the split (each family's measured thresholds stand beside its policy object).
@@ -45,6 +48,8 @@ inline void plan_plain(long long tiles, const SplitPolicy &p, GemmSplit *sp, lon
     sp->nsplit = 0;
     sp->stride = 1;
     sp->units = 0;
+    sp->front = 0;
+    sp->first_split = 0;
     *grid = tiles;
 }
 
@@ -75,6 +80,58 @@ inline bool plan_split(long long tiles, int slots, int nkt, const SplitPolicy &p
     *grid = sp->whole_rounds ? slots : (sp->nsplit > 0 ? sp->nsplit : 1);
     sp->stride = (int)(*grid / sp->nsplit) > 0 ? (int)(*grid / sp->nsplit) : 1;
     return true;
+}
+
+// ---- the remainder plan (gemm_x6.hip) ----------------------------------------------------------------------------------------------------------
+// For a plain grid that ends a handful of tiles past a whole number of rounds of CUs -- M = 8 x 1370 rows are 86 row tiles, so the ViT-S linears are
+// 256 + 2, 768 + 6 and 1024 + 8 tiles on 256 CUs -- where plan_split declines (shallow tiles) or would cut every tile.  Those L = tiles mod CUs tiles cost a
+// round of their own (a CU that carries one more tile than the others sets the launch's time).  Here only they are split: the LAST L tile indices
+// are cut along k into `nsplit` runs of `chunk` k-tiles, the other tiles stay whole, and the grid is nsplit + whole tiles workgroups.  The first
+// nsplit RAW block indices own run blockIdx.x and nothing else, so the hardware starts the pieces first and deals them round-robin over the XCDs;
+// their hand-off and merge (the same split_slot / split_handoff / split_piece path) finish under the first round of whole tiles instead of forming
+// a tail.  Every later workgroup computes one whole tile, dispatched dynamically like the plain grid's.
+struct RemainderPolicy {
+    int left_div;     // by policy only L <= CUs / left_div leftover tiles are worth it (more: the pieces themselves fill a good part of a round),
+                      // and only grids that are resident at once (grid <= CUs x workgroups per CU): those cleared the spread of their repetitions
+    int run_div;      // run length = k-tiles / run_div ...
+    int min_run;      // ... but at least this many k-tiles (a piece costs a prologue, 64 KB of stores and a counter add); shallower tiles run plain
+    int runs_per_cu;  // runs (two piece slots each) that gemm_workspace() holds per CU at this family's slot size
+    int counters;
+};
+
+// Fills sp (all but its pointers and group_m) and the grid.  `everywhere`: wherever the walk is supported (any L > 0), not only where the policy
+// expects a gain.  false: the plan does not apply; sp and grid are untouched.
+inline bool plan_remainder(long long tiles, int nkt, int cus, int wgs_per_cu, bool everywhere, const RemainderPolicy &p, GemmSplit *sp, long long *grid) {
+    if (cus <= 0 || wgs_per_cu <= 0 || tiles < cus || nkt < p.min_run) return false;
+    const long long left = tiles % cus;
+    if (left == 0 || left > p.counters || (!everywhere && left * p.left_div > cus)) return false;
+    const long long units = left * nkt;
+    // every run is resident in the first wave of the dispatch and has its two slots in the workspace
+    const long long cap = (long long)cus * (wgs_per_cu < p.runs_per_cu ? wgs_per_cu : p.runs_per_cu);
+    long long chunk = nkt / p.run_div > p.min_run ? nkt / p.run_div : p.min_run;
+    if ((units + cap - 1) / cap > chunk) chunk = (units + cap - 1) / cap;
+    const long long nsplit = (units + chunk - 1) / chunk;
+    if (!everywhere && nsplit + (tiles - left) > (long long)cus * wgs_per_cu) return false;
+    sp->whole_rounds = 1;
+    sp->chunk = (int)chunk;
+    sp->nsplit = (int)nsplit;
+    sp->stride = 1;
+    sp->units = units;
+    sp->front = 1;
+    sp->first_split = (int)(tiles - left);
+    *grid = sp->nsplit + (tiles - left);
+    return true;
+}
+
+// The whole tile of raw block index b >= nsplit in a remainder grid of G workgroups.  Blocks b and b + 8 share an XCD; as in xcd_remap each XCD gets
+// a contiguous run of tile indices, counted over the whole-tile blocks only: a bijection from [nsplit, G) onto [0, G - nsplit).
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline int front_whole_tile(int b, int G, int nsplit) {
+    const int x = b & 7;
+    const int before = ((G >> 3) * x + (x < (G & 7) ? x : (G & 7))) - ((nsplit >> 3) * x + (x < (nsplit & 7) ? x : (nsplit & 7)));  // whole blocks of XCDs < x
+    return before + (b >> 3) - ((nsplit + 7 - x) >> 3);
 }
 
 // floats of workspace a split launch needs: the counters, then two slots per run

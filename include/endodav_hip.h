@@ -759,8 +759,19 @@ int edv_bilinear_add(const float *x_dev, const float *add_dev, float *y_dev, int
  * queried.  Touches no device.  kind: 0 LDS-DMA GEMM, 1 bf16x6 GEMM, 2 3x3 convolution (tiles of k_tiles k-tiles), 3 spatial attention
  * forward / backward (tasks of k_tiles key tiles).  It runs the launch path's own policy (environment knobs included) as for a launch with
  * a workspace.  out = { 1 split / 0 plain, grid, whole_rounds, chunk, nsplit, stride (kind 3: leftover tasks), units,
- * workspace floats the plan needs (kinds 0-2; kind 3: pieces, to be multiplied by the caller's rows x columns) }. */
+ * workspace floats the plan needs (kinds 0-2; kind 3: pieces, to be multiplied by the caller's rows x columns) }.
+ * Added later (additive): kind 4, the bf16x6 GEMM's remainder plan as edv_gemm_x6 would decide it.  slots = CUs; ON ENTRY out[0] = resident
+ * workgroups per CU and out[1] = the mode of edv_set_x6_remainder (1 or 2).  out = { 1 remainder plan / 0 another plan (then all zero), grid,
+ * first split tile = whole tiles, chunk, nsplit, split tiles, units, workspace floats }.  kind 5: the whole tile that raw block index
+ * tiles_or_tasks computes in a remainder grid of `slots` workgroups whose first k_tiles own runs; out[0] = the tile. */
 int edv_split_plan(int32_t kind, int64_t tiles_or_tasks, int32_t slots, int32_t k_tiles, int64_t out[8]);
+
+/* Additive: process-wide switch of the bf16x6 GEMM's remainder plan, read at every edv_gemm_x6 / engine launch.  A plain grid that ends a few
+ * tiles past a whole number of rounds of CUs splits only those tiles along k and starts their pieces first.  mode 0 = off, 1 = by policy (the
+ * default: at most CUs / 16 tiles past a round, and the whole grid resident at once), 2 = wherever the walk is supported (tests, A/B runs).
+ * cus > 0 plans for that many CUs instead of the device's (tests: ten-tile problems take the path at cus = 8); 0, or more than the device
+ * has, = the device's count.  Tiles that are not split keep their bits in every mode. */
+int edv_set_x6_remainder(int32_t mode, int32_t cus);
 
 #ifdef __cplusplus
 }
