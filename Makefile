@@ -14,7 +14,7 @@ all: $(OUT)
 # first canonicalised by an extra v_max_f32 (VALU instructions cost matrix-pipe time)
 build/attn_spatial.o: HIPFLAGS += -fno-honor-nans
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/ops.hpp $(CSRC)/common.hpp $(CSRC)/gemm_common.hpp $(CSRC)/streamk_plan.hpp $(CSRC)/loss_common.hpp $(CSRC)/engine.hpp $(CSRC)/resample_coord.hpp $(CSRC)/cloud_common.hpp $(CSRC)/tsdf_common.hpp include/endodav_hip.h
+build/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/endodav_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -128,6 +129,25 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the sum over a block of 256 threads of Q per-thread partials -> dst[0..Q): wave butterfly, then the four waves in order
+template <int Q>
+__device__ __forceinline__ void block_sum_store(double (&a)[Q], double *dst) {
+    __shared__ double red[4][Q];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        a[q] = wave_sum_f64(a[q]);
+        if (lane == 0) red[wave][q] = a[q];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < Q) dst[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
 
 // exact-erf GELU, the nn.GELU() / F.gelu default used everywhere in the reference
 // (layers/block.py:58, motion_module/attention.py:378)
@@ -140,5 +160,10 @@ inline int env_int(const char *name, int dflt) {
 }
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// blocks of 256 threads for a grid-stride loop over `groups` items: one item a thread, at least one block and at most `cap`
+inline int blocks_for(long long groups, int cap) { return (int)std::max<long long>(1, std::min<long long>((groups + 255) / 256, cap)); }
 
 }  // namespace edv

@@ -1,8 +1,7 @@
 // Video-depth evaluation on the device (reference evaluate_depth_video.py:163-215 with utils/utils.py:112-133, utils/layers.py:11-20 and
 // utils/eval_utils.py:63-143,265-282; host counterpart evaluate.clip_metrics_host).  A clip is [n, h, w] fp32.
-//   masked_median     exact radix select on the order-preserving integer image of the float bits: four 8-bit histogram passes over the
-//                     elements with lo < gate < hi, LDS counters per block, 64-bit integer counters per clip.  Both middle order statistics
-//                     are followed at once, so an even count costs no extra pass.  np.median's bits.
+//   masked_median     the exact radix select of select_common.hpp over the elements with lo < gate < hi, as a batch of one.  Both middle
+//                     order statistics are followed at once, so an even count costs no extra pass.  np.median's bits.
 //   metrics_pred      disparity -> depth, the alignment ("scale": ratio of medians; "scale_shift": medians and mean absolute deviations),
 //                     the scale factor and the clip.  Every fp32 operation is the host's, in the host's order; the alignment scalars stay in
 //                     device memory (doubles that hold fp32 values exactly, and the count).
@@ -21,11 +20,10 @@
 
 #pragma clang fp contract(off)
 
+#include "select_common.hpp"  // SelState, select_hist_kernel, select_narrow, order_key, key_value, in_gate, load_group: shared with render.hip
+
 namespace edv {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u64 = unsigned long long;
 
 constexpr int RED_BLOCKS = 128;      // blocks per frame of the per-frame reductions (1024 x 1280: 40 pixels per thread)
 constexpr int FRAME_CHUNK = 8;       // frames per launch of the error kernel
@@ -35,81 +33,15 @@ constexpr int ERR_Q = 8, TMP_Q = 3;
 constexpr float MIN_DEPTH = 1e-3f, ALIGN_MAX_DEPTH = 150.0f, SPLAT_EPS_F = 1e-6f;
 constexpr double SPLAT_EPS = 1e-6;
 
-struct SelState {
-    u64 hist[2][256];
-    u64 rank[2];
-    u64 total;
-    unsigned prefix[2];
-};
 constexpr size_t WS_STATE = 8192;                                                  // SelState, padded
 constexpr size_t WS_PARTIALS = (size_t)FRAME_CHUNK * RED_BLOCKS * ERR_Q * 8;       // the largest of the partial arrays (64 KiB)
 constexpr size_t WS_HEAD = WS_STATE + WS_PARTIALS;
 static_assert(sizeof(SelState) <= WS_STATE);
 static_assert((size_t)FLAT_MAX_BLOCKS * 8 <= WS_PARTIALS && (size_t)2 * PAIR_CHUNK * RED_BLOCKS * TMP_Q * 8 <= WS_PARTIALS);
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the block's sum of Q per-thread partials -> dst[0..Q): wave butterfly, then the four waves in order
-template <int Q>
-__device__ __forceinline__ void block_sum_store(double (&a)[Q], double *dst) {
-    __shared__ double red[4][Q];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        a[q] = wave_sum_f64(a[q]);
-        if (lane == 0) red[wave][q] = a[q];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < Q) dst[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-
-__device__ __forceinline__ bool in_gate(float g, float lo, float hi) { return lo < g && g < hi; }  // NaN fails both, as on the host
-
-// ---- masked median ----------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned order_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// one pass: of the gated elements whose key starts with prefix[s], count the next 8 bits.  x may alias gate.
-template <int VW>
-__global__ __launch_bounds__(256) void select_hist_kernel(const float *x, const float *gate, long long count, float lo, float hi, int shift, SelState *s) {
-    __shared__ unsigned h[2][256];
-    h[0][threadIdx.x] = 0, h[1][threadIdx.x] = 0;
-    __syncthreads();
-    const unsigned hmask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
-    const unsigned p0 = s->prefix[0], p1 = s->prefix[1];
-    const bool two = p0 != p1;
-    const long long groups = count / VW;
-    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
-        float xv[VW], gv[VW];
-        if constexpr (VW == 4) {
-            const f32x4 a = reinterpret_cast<const f32x4 *>(x)[g], b = reinterpret_cast<const f32x4 *>(gate)[g];
-            xv[0] = a.x, xv[1] = a.y, xv[2] = a.z, xv[3] = a.w;
-            gv[0] = b.x, gv[1] = b.y, gv[2] = b.z, gv[3] = b.w;
-        } else {
-            xv[0] = x[g], gv[0] = gate[g];
-        }
-#pragma unroll
-        for (int j = 0; j < VW; ++j) {
-            if (!in_gate(gv[j], lo, hi)) continue;
-            const unsigned k = order_key(xv[j]);
-            const unsigned bin = (k >> shift) & 255u;
-            if ((k & hmask) == p0) atomicAdd(&h[0][bin], 1u);
-            if (two && (k & hmask) == p1) atomicAdd(&h[1][bin], 1u);
-        }
-    }
-    __syncthreads();
-    if (h[0][threadIdx.x]) atomicAdd(&s->hist[0][threadIdx.x], (u64)h[0][threadIdx.x]);
-    if (two && h[1][threadIdx.x]) atomicAdd(&s->hist[1][threadIdx.x], (u64)h[1][threadIdx.x]);
-}
-
-// one block: narrows both order statistics by the 8 bits just counted, clears the counters, and after the last pass writes the result
+// ---- masked median (the select itself is select_common.hpp) --------------------------------------------------------------------------------
+// one block: after the first pass the total and from it the two middle ranks; narrows, clears the counters, and after the last pass writes the
+// median and the count
 __global__ __launch_bounds__(256) void select_step_kernel(SelState *s, int shift, double *out_median, double *out_count) {
     if (threadIdx.x == 0) {
         if (shift == 24) {
@@ -119,21 +51,7 @@ __global__ __launch_bounds__(256) void select_step_kernel(SelState *s, int shift
             s->rank[0] = total ? (total - 1) / 2 : 0;
             s->rank[1] = total / 2;
         }
-        if (s->total != 0) {
-            const bool two = s->prefix[0] != s->prefix[1];
-            unsigned np[2];
-            u64 nr[2];
-            for (int sel = 0; sel < 2; ++sel) {
-                const u64 *h = s->hist[two ? sel : 0];
-                u64 r = s->rank[sel];
-                int b = 0;
-                while (b < 255 && r >= h[b]) r -= h[b], ++b;
-                np[sel] = s->prefix[sel] | ((unsigned)b << shift);
-                nr[sel] = r;
-            }
-            s->prefix[0] = np[0], s->prefix[1] = np[1];
-            s->rank[0] = nr[0], s->rank[1] = nr[1];
-        }
+        if (s->total != 0) select_narrow(s, shift);
         if (shift == 0) {
             float med = std::numeric_limits<float>::quiet_NaN();
             if (s->total != 0) {
@@ -148,19 +66,17 @@ __global__ __launch_bounds__(256) void select_step_kernel(SelState *s, int shift
     s->hist[0][threadIdx.x] = 0, s->hist[1][threadIdx.x] = 0;
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline int flat_blocks(long long groups) { return (int)std::max<long long>(1, std::min<long long>((groups + 255) / 256, FLAT_MAX_BLOCKS)); }
-
+// a batch of one
 int median_into(const float *x, const float *gate, long long count, float lo, float hi, double *out_median, double *out_count, void *ws, hipStream_t stream) {
     SelState *s = static_cast<SelState *>(ws);
     EDV_HIP(hipMemsetAsync(s, 0, sizeof(SelState), stream));
-    const bool vec = count % 4 == 0 && aligned16(x) && aligned16(gate);
-    const int blocks = flat_blocks(count / (vec ? 4 : 1));
+    const bool vec = count % 4 == 0 && aligned_to(x, 16) && aligned_to(gate, 16);
+    const int blocks = blocks_for(count / (vec ? 4 : 1), FLAT_MAX_BLOCKS);
     for (int shift = 24; shift >= 0; shift -= 8) {
         if (vec)
-            EDV_LAUNCH(select_hist_kernel<4>, dim3(blocks), dim3(256), 0, stream, x, gate, count, lo, hi, shift, s);
+            EDV_LAUNCH((select_hist_kernel<4, true>), dim3(blocks), dim3(256), 0, stream, x, gate, count, lo, hi, shift, s);
         else
-            EDV_LAUNCH(select_hist_kernel<1>, dim3(blocks), dim3(256), 0, stream, x, gate, count, lo, hi, shift, s);
+            EDV_LAUNCH((select_hist_kernel<1, true>), dim3(blocks), dim3(256), 0, stream, x, gate, count, lo, hi, shift, s);
         EDV_LAUNCH_OK();
         EDV_LAUNCH(select_step_kernel, dim3(1), dim3(256), 0, stream, s, shift, out_median, out_count);
         EDV_LAUNCH_OK();
@@ -196,13 +112,7 @@ __global__ __launch_bounds__(256) void absdev_kernel(const float *__restrict__ x
     double a[1] = {0.0};
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
         float xv[VW], gv[VW];
-        if constexpr (VW == 4) {
-            const f32x4 p = reinterpret_cast<const f32x4 *>(x)[g], q = reinterpret_cast<const f32x4 *>(gate)[g];
-            xv[0] = p.x, xv[1] = p.y, xv[2] = p.z, xv[3] = p.w;
-            gv[0] = q.x, gv[1] = q.y, gv[2] = q.z, gv[3] = q.w;
-        } else {
-            xv[0] = x[g], gv[0] = gate[g];
-        }
+        load_group<VW>(x, g, xv), load_group<VW>(gate, g, gv);
 #pragma unroll
         for (int j = 0; j < VW; ++j)
             if (in_gate(gv[j], MIN_DEPTH, ALIGN_MAX_DEPTH)) a[0] += (double)fabsf(xv[j] - t);
@@ -227,12 +137,7 @@ __global__ __launch_bounds__(256) void apply_kernel(float *__restrict__ pred, lo
     const long long groups = count / VW;
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
         float v[VW];
-        if constexpr (VW == 4) {
-            const f32x4 p = reinterpret_cast<const f32x4 *>(pred)[g];
-            v[0] = p.x, v[1] = p.y, v[2] = p.z, v[3] = p.w;
-        } else {
-            v[0] = pred[g];
-        }
+        load_group<VW>(pred, g, v);
 #pragma unroll
         for (int j = 0; j < VW; ++j) {
             float p = v[j];
@@ -410,8 +315,8 @@ int metrics_pred(const float *disp, const float *gt, float *pred, long long n, i
     const long long count = n * h * w;
     // disp_to_depth: python floats lo = 1 / max, hi = 1 / min; numpy rounds lo and (hi - lo) to fp32 when they meet the float32 map
     const double lo = 1.0 / max_depth, hi = 1.0 / min_depth;
-    const bool vec = count % 4 == 0 && aligned16(disp) && aligned16(gt) && aligned16(pred);
-    const int blocks = flat_blocks(count / (vec ? 4 : 1));
+    const bool vec = count % 4 == 0 && aligned_to(disp, 16) && aligned_to(gt, 16) && aligned_to(pred, 16);
+    const int blocks = blocks_for(count / (vec ? 4 : 1), FLAT_MAX_BLOCKS);
     double *partials = reinterpret_cast<double *>(static_cast<char *>(ws) + WS_STATE);
     EDV_HIP(hipMemsetAsync(scal, 0, S_LEN * sizeof(double), stream));
     if (vec)

@@ -5,8 +5,8 @@
 //                  by wave ballot and popcount, one 64-bit count per tile in the workspace
 //                  one workgroup: exclusive 64-bit scan of the counts over all tiles in frame-major order, in place; offsets[f] = the points of
 //                  the frames before f, offsets[n] = the total
-//   cloud_scatter  the same tiles: the predicate again, the rank of every kept pixel inside its tile (ballot and lane prefix in a wave, an LDS
-//                  prefix over waves and iterations), the point in fp64, and element stores of point g = tile offset + rank when g < capacity
+//   cloud_scatter  the same tiles: the predicate again, the rank of every kept pixel inside its tile (compact_common.hpp's tile_ranks), the
+//                  point in fp64, and element stores of point g = tile offset + rank when g < capacity
 // No workgroup waits for another inside a launch and there are no atomics at all: the same input gives the same bits on every call.  The output
 // of a tile starts at an arbitrary 12-byte (points) or 1-byte (colours) boundary; every store is one float or one byte of exactly one point, so
 // no two workgroups ever write the same dword.
@@ -17,7 +17,8 @@
 
 #pragma clang fp contract(off)
 
-#include "cloud_common.hpp"  // depth_value, kept, cloud_scan_kernel, check_selection: shared with tsdf.hip
+#include "cloud_common.hpp"    // depth_value, kept, check_selection: shared with tsdf.hip
+#include "compact_common.hpp"  // wave_count, tile_count_store, exclusive_scan_kernel, tile_ranks: shared with tsdf.hip and tsdf_mesh.hip
 
 namespace edv {
 namespace {
@@ -37,7 +38,6 @@ __device__ __forceinline__ int source_pixel(const CloudSel &s, int ow, unsigned 
 // grid (tiles per frame, frames).  UNIT: step == 1, where the source pixel is the output pixel
 template <bool UNIT>
 __global__ __launch_bounds__(CLOUD_THREADS) void cloud_count_kernel(CloudSel s, int ow, unsigned grid_pixels, u64 *__restrict__ counts) {
-    __shared__ unsigned red[CLOUD_WAVES];
     const long long f = blockIdx.y;
     const float *xf = s.x + f * s.h * s.w;
     const uint8_t *mf = s.mask ? s.mask + f * s.mask_stride : nullptr;
@@ -58,17 +58,9 @@ __global__ __launch_bounds__(CLOUD_THREADS) void cloud_count_kernel(CloudSel s, 
 #pragma unroll
     for (int it = 0; it < CLOUD_ITERS; ++it) {
         float z;
-        c += (unsigned)__popcll(__ballot(kept(s, x[it], m[it], z)));
+        c += wave_count<1>(kept(s, x[it], m[it], z));
     }
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    if (lane == 0) red[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-#pragma unroll
-        for (int v = 0; v < CLOUD_WAVES; ++v) t += red[v];
-        counts[f * gridDim.x + blockIdx.x] = t;
-    }
+    tile_count_store<CLOUD_WAVES, 1>({c}, {counts}, f * gridDim.x + blockIdx.x);
 }
 
 // grid (tiles per frame, frames)
@@ -76,18 +68,15 @@ __global__ __launch_bounds__(CLOUD_THREADS) void cloud_scatter_kernel(CloudSel s
                                                                       const uint8_t *__restrict__ frames, const long long *__restrict__ offsets,
                                                                       const u64 *__restrict__ tile_offsets, float *__restrict__ points,
                                                                       uint8_t *__restrict__ colors, u64 capacity) {
-    __shared__ unsigned cnt[CLOUD_ITERS][CLOUD_WAVES];
     const long long f = blockIdx.y;
     const u64 tile_base = tile_offsets[f * gridDim.x + blockIdx.x];
     // uniform over the workgroup: a frame without points, or a tile that starts behind the capacity, has nothing to write
     if (offsets[f + 1] == offsets[f] || tile_base >= capacity) return;
     const float *xf = s.x + f * s.h * s.w;
     const uint8_t *mf = s.mask ? s.mask + f * s.mask_stride : nullptr;
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
     float z[CLOUD_ITERS];
-    unsigned m[CLOUD_ITERS];
+    unsigned m[CLOUD_ITERS], keep[CLOUD_ITERS], rank[CLOUD_ITERS];
     int p[CLOUD_ITERS], ox[CLOUD_ITERS], oy[CLOUD_ITERS];
-    u64 ballot[CLOUD_ITERS];
 #pragma unroll
     for (int it = 0; it < CLOUD_ITERS; ++it) {  // all loads of the tile first, so that they are in flight together
         const unsigned q = blockIdx.x * (unsigned)CLOUD_TILE + it * CLOUD_THREADS + threadIdx.x;
@@ -98,22 +87,8 @@ __global__ __launch_bounds__(CLOUD_THREADS) void cloud_scatter_kernel(CloudSel s
         }
     }
 #pragma unroll
-    for (int it = 0; it < CLOUD_ITERS; ++it) {
-        ballot[it] = __ballot(kept(s, z[it], m[it], z[it]));
-        if (lane == 0) cnt[it][wave] = (unsigned)__popcll(ballot[it]);
-    }
-    __syncthreads();
-    // rank of the first kept pixel of (iteration, wave): pixels are ordered by iteration, then wave, then lane
-    unsigned first[CLOUD_ITERS] = {}, run = 0;
-#pragma unroll
-    for (int it = 0; it < CLOUD_ITERS; ++it) {
-#pragma unroll
-        for (int v = 0; v < CLOUD_WAVES; ++v) {
-            if (v == wave) first[it] = run;
-            run += cnt[it][v];
-        }
-    }
-    if (run == 0) return;
+    for (int it = 0; it < CLOUD_ITERS; ++it) keep[it] = kept(s, z[it], m[it], z[it]);
+    if (tile_ranks<CLOUD_ITERS, CLOUD_WAVES, 1>(keep, rank) == 0) return;
     const double *cam = cams + f * cam_stride;
     double Kinv[9], R[9], t[3];
 #pragma unroll
@@ -122,11 +97,10 @@ __global__ __launch_bounds__(CLOUD_THREADS) void cloud_scatter_kernel(CloudSel s
     for (int i = 0; i < 3; ++i) t[i] = cam[18 + i];
     const bool colour = frames && colors;
     const uint8_t *ff = colour ? frames + f * s.h * s.w * 3 : nullptr;
-    const u64 below = (1ull << lane) - 1ull;
 #pragma unroll
     for (int it = 0; it < CLOUD_ITERS; ++it) {
-        if (!((ballot[it] >> lane) & 1ull)) continue;
-        const u64 g = tile_base + first[it] + (unsigned)__popcll(ballot[it] & below);
+        if (!keep[it]) continue;
+        const u64 g = tile_base + rank[it];
         if (g >= capacity) continue;
         const double u = ((double)ox[it] + 0.5) * (double)s.step, v = ((double)oy[it] + 0.5) * (double)s.step;
         double l[3];
@@ -184,7 +158,7 @@ int cloud_count(const CloudSel &s, long long *offsets, void *ws, size_t ws_bytes
     else
         EDV_LAUNCH(cloud_count_kernel<false>, grid, dim3(CLOUD_THREADS), 0, stream, s, g.ow, g.pixels, counts);
     EDV_LAUNCH_OK();
-    EDV_LAUNCH(cloud_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, counts, s.n * g.tiles_per_frame, g.tiles_per_frame, offsets, s.n);
+    EDV_LAUNCH(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, counts, s.n * g.tiles_per_frame, g.tiles_per_frame, offsets, s.n);
     EDV_LAUNCH_OK();
     return 0;
 }

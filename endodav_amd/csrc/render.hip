@@ -1,11 +1,10 @@
 // Colour-mapped depth on the device: the numpy of the reference's three renderers (utils/eval_utils.py:284-295 save_video,
 // evaluate_depth_video.py:32-36 render_depth, test_simple.py:156-167), as two steps over a clip [n, h, w] fp32.
 //   render_range     (lo, hi) per frame: the frame's or the whole clip's minimum and maximum, or two order statistics per frame.  All of them
-//                    compare the order-preserving integer image of the float bits (metrics.hip's order_key), so they are exact, independent of
-//                    the order of the reduction, and use integer atomics only: the same input gives the same bits on every call.
-//                    The order statistics are metrics.hip's radix select (four 8-bit histogram passes, both statistics followed at once, LDS
-//                    counters flushed with 64-bit atomics), batched: the frame is blockIdx.y and every frame has a select state of its own in
-//                    the workspace, so a pass is one launch for all frames of a chunk.
+//                    compare the order-preserving integer image of the float bits (select_common.hpp's order_key), so they are exact,
+//                    independent of the order of the reduction, and use integer atomics only: the same input gives the same bits on every call.
+//                    The order statistics are the radix select of select_common.hpp, ungated, with the frames of a chunk as its batch: every
+//                    frame has a select state of its own in the workspace, so a pass is one launch for all frames of a chunk.
 //   render_colorize  idx = trunc((x - lo) / ((hi - lo) + eps) * 255) -> lut[idx], 3 bytes a pixel.  The table lives in LDS as one dword per
 //                    entry.  A sub-dword global store costs several times a dword store per byte on this part, so where the shape allows it
 //                    a thread owns four pixels: one 16-byte load, twelve output bytes assembled in registers and stored as three whole dwords
@@ -17,11 +16,10 @@
 
 #pragma clang fp contract(off)
 
+#include "select_common.hpp"  // SelState, select_hist_kernel, select_narrow, order_key, key_value, load_group: shared with metrics.hip
+
 namespace edv {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u64 = unsigned long long;
 
 constexpr int RANGE_CHUNK = 64;        // frames per launch of the range kernels: the workspace stops growing there
 constexpr int FRAME_BLOCKS = 128;      // blocks per frame at most (1024 x 1280 in groups of 4: 10 groups per thread)
@@ -29,33 +27,11 @@ constexpr int FLAT_MAX_BLOCKS = 2048;  // blocks of the whole-clip reduction
 constexpr int COLOR_BLOCKS = 1024;     // blocks per frame of the colouring at most
 constexpr int COLOR_FRAMES = 32768;    // frames per launch of the colouring (blockIdx.y)
 
-struct alignas(16) SelState {
-    u64 hist[2][256];
-    u64 rank[2];
-    unsigned prefix[2];
-    unsigned pad[2];
-};
 // maxima of key and of ~key: zero is the identity of both, so a memset initialises them
 struct MinMax {
     unsigned hi_key, lo_inv;
 };
 static_assert(sizeof(MinMax) * RANGE_CHUNK <= sizeof(SelState));
-
-__device__ __forceinline__ unsigned order_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-template <int VW>
-__device__ __forceinline__ void load_group(const float *x, long long g, float (&v)[VW]) {
-    if constexpr (VW == 4) {
-        const f32x4 a = reinterpret_cast<const f32x4 *>(x)[g];
-        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
-    } else {
-        v[0] = x[g];
-    }
-}
 
 // ---- minimum and maximum ------------------------------------------------------------------------------------------------------------------
 // grid (blocks, frames): frame blockIdx.y is x[blockIdx.y * elems ..), its extremes go to mm[blockIdx.y]
@@ -98,55 +74,15 @@ __global__ __launch_bounds__(256) void minmax_final_kernel(const MinMax *__restr
 }
 
 // ---- two order statistics per frame ---------------------------------------------------------------------------------------------------------
-// one pass, grid (blocks, frames): of frame blockIdx.y's elements whose key starts with prefix[s], count the next 8 bits
-template <int VW>
-__global__ __launch_bounds__(256) void select_hist_kernel(const float *__restrict__ x, int E, int shift, SelState *states) {
-    __shared__ unsigned h[2][256];
-    h[0][threadIdx.x] = 0, h[1][threadIdx.x] = 0;
-    __syncthreads();
-    SelState *s = states + blockIdx.y;
-    const float *xf = x + (long long)blockIdx.y * E;
-    const unsigned hmask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
-    const unsigned p0 = s->prefix[0], p1 = s->prefix[1];
-    const bool two = p0 != p1;
-    const int groups = E / VW;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < groups; g += gridDim.x * 256) {
-        float v[VW];
-        load_group<VW>(xf, g, v);
-#pragma unroll
-        for (int j = 0; j < VW; ++j) {
-            const unsigned k = order_key(v[j]);
-            const unsigned bin = (k >> shift) & 255u;
-            if ((k & hmask) == p0) atomicAdd(&h[0][bin], 1u);
-            if (two && (k & hmask) == p1) atomicAdd(&h[1][bin], 1u);
-        }
-    }
-    __syncthreads();
-    if (h[0][threadIdx.x]) atomicAdd(&s->hist[0][threadIdx.x], (u64)h[0][threadIdx.x]);
-    if (two && h[1][threadIdx.x]) atomicAdd(&s->hist[1][threadIdx.x], (u64)h[1][threadIdx.x]);
-}
-
-// one block per frame: narrows both statistics by the 8 bits just counted, clears the counters, and after the last pass writes (lo, hi)
+// one block per frame: takes the two ranks before the first narrowing, narrows, clears the counters, and after the last pass writes (lo, hi)
 __global__ __launch_bounds__(256) void select_step_kernel(SelState *states, int shift, u64 rank_lo, u64 rank_hi, float *__restrict__ range) {
     SelState *s = states + blockIdx.x;
     if (threadIdx.x == 0) {
         if (shift == 24) s->rank[0] = rank_lo, s->rank[1] = rank_hi;  // the state was zeroed: both prefixes are empty
-        const bool two = s->prefix[0] != s->prefix[1];
-        unsigned np[2];
-        u64 nr[2];
-        for (int sel = 0; sel < 2; ++sel) {
-            const u64 *h = s->hist[two ? sel : 0];
-            u64 r = s->rank[sel];
-            int b = 0;
-            while (b < 255 && r >= h[b]) r -= h[b], ++b;
-            np[sel] = s->prefix[sel] | ((unsigned)b << shift);
-            nr[sel] = r;
-        }
-        s->prefix[0] = np[0], s->prefix[1] = np[1];
-        s->rank[0] = nr[0], s->rank[1] = nr[1];
+        select_narrow(s, shift);
         if (shift == 0) {
-            range[2 * blockIdx.x] = key_value(np[0]);
-            range[2 * blockIdx.x + 1] = key_value(np[1]);
+            range[2 * blockIdx.x] = key_value(s->prefix[0]);
+            range[2 * blockIdx.x + 1] = key_value(s->prefix[1]);
         }
     }
     __syncthreads();
@@ -225,9 +161,6 @@ __global__ __launch_bounds__(256) void colorize1_kernel(const float *__restrict_
     }
 }
 
-inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline int blocks_for(long long groups, int cap) { return (int)std::max<long long>(1, std::min<long long>((groups + 255) / 256, cap)); }
-
 inline int check_clip(long long n, int h, int w) {
     EDV_CHECK(n >= 1 && h >= 1 && w >= 1, "empty clip");
     EDV_CHECK((long long)h * w < (1ll << 31) - 256ll * COLOR_BLOCKS, "a frame beyond 2^31 pixels");
@@ -282,9 +215,9 @@ int render_range(const float *x, long long n, int h, int w, int mode, long long 
         EDV_HIP(hipMemsetAsync(states, 0, sizeof(SelState) * frames, stream));
         for (int shift = 24; shift >= 0; shift -= 8) {
             if (vec)
-                EDV_LAUNCH(select_hist_kernel<4>, dim3(blocks, frames), dim3(256), 0, stream, xc, E, shift, states);
+                EDV_LAUNCH((select_hist_kernel<4, false>), dim3(blocks, frames), dim3(256), 0, stream, xc, (const float *)nullptr, (long long)E, 0.f, 0.f, shift, states);
             else
-                EDV_LAUNCH(select_hist_kernel<1>, dim3(blocks, frames), dim3(256), 0, stream, xc, E, shift, states);
+                EDV_LAUNCH((select_hist_kernel<1, false>), dim3(blocks, frames), dim3(256), 0, stream, xc, (const float *)nullptr, (long long)E, 0.f, 0.f, shift, states);
             EDV_LAUNCH_OK();
             EDV_LAUNCH(select_step_kernel, dim3(frames), dim3(256), 0, stream, states, shift, (u64)rank_lo, (u64)rank_hi, rc);
             EDV_LAUNCH_OK();

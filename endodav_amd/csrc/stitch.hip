@@ -17,11 +17,10 @@
 // same reason as in resample.hip: an upsampled value must not depend on which products the compiler fuses
 #pragma clang fp contract(off)
 #include "resample_coord.hpp"
+#include "select_common.hpp"  // load_group
 
 namespace edv {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int W_LEN = 32, W_OVERLAP = 10, W_INTERP = 8;  // INFER_LEN, OVERLAP, INTERP_LEN of the reference's endodav.py
 constexpr int W_ALIGN = W_OVERLAP - W_INTERP;            // the first overlap slot that is fitted and faded
@@ -41,46 +40,30 @@ __device__ __forceinline__ float up_at(const Upsample &u, int slot, int oy, int 
     return bilinear_tap(u.disp + (long long)slot * u.ih * u.iw, u.iw, y0, y1, x0, x1, ly, lx);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // partials [gridDim.x][4]: sum p*p, sum p, sum p*t, sum t of the pixels this block visited
 template <int VW>
 __global__ __launch_bounds__(256) void stitch_fit_kernel(Upsample u, const float *__restrict__ tail, double *__restrict__ partials) {
     const long long E = (long long)u.fh * u.fw;
     const long long groups = (long long)W_INTERP * E / VW;
-    double a_pp = 0.0, a_p = 0.0, a_pt = 0.0, a_t = 0.0;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
         const long long e0 = g * VW;
         const int fr = (int)(e0 / E);
         const int r = (int)(e0 - fr * E);
         int oy = r / u.fw, ox = r - oy * u.fw;
         float t[VW];
-        if constexpr (VW == 4) {
-            const f32x4 tv = reinterpret_cast<const f32x4 *>(tail)[g];
-            t[0] = tv.x, t[1] = tv.y, t[2] = tv.z, t[3] = tv.w;
-        } else {
-            t[0] = tail[g];
-        }
+        load_group<VW>(tail, g, t);
 #pragma unroll
         for (int j = 0; j < VW; ++j) {
             const double p = (double)up_at(u, W_ALIGN + fr, oy, ox), tt = (double)t[j];
-            a_pp += p * p;
-            a_p += p;
-            a_pt += p * tt;
-            a_t += tt;
+            a[0] += p * p;
+            a[1] += p;
+            a[2] += p * tt;
+            a[3] += tt;
             if (++ox == u.fw) ox = 0, ++oy;
         }
     }
-    __shared__ double red[4][4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    a_pp = wave_sum_f64(a_pp), a_p = wave_sum_f64(a_p), a_pt = wave_sum_f64(a_pt), a_t = wave_sum_f64(a_t);
-    if (lane == 0) red[wave][0] = a_pp, red[wave][1] = a_p, red[wave][2] = a_pt, red[wave][3] = a_t;
-    __syncthreads();
-    if (threadIdx.x < 4) partials[(long long)blockIdx.x * 4 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    block_sum_store<4>(a, partials + (long long)blockIdx.x * 4);
 }
 
 // one block: the per-block partials in a fixed order, then the 2x2 normal equations of utils/util.py:40-63 (mask = 1) in fp64
@@ -166,8 +149,6 @@ __global__ __launch_bounds__(256) void stitch_apply_kernel(Upsample u, const flo
     }
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 inline int check_shapes(int ih, int iw, int fh, int fw) {
     EDV_CHECK(ih > 0 && iw > 0 && fh > 0 && fw > 0, "empty problem");
     EDV_CHECK((long long)W_LEN * ih * iw < (1ll << 31) && (long long)fh * fw < (1ll << 31), "a map beyond 2^31 pixels");
@@ -184,9 +165,9 @@ int stitch_fit(const float *disp, int ih, int iw, const float *tail, int fh, int
     EDV_CHECK(ws_bytes >= stitch_workspace() && (reinterpret_cast<uintptr_t>(ws) & 7) == 0, "workspace too small or not 8-byte aligned (edv_stitch_workspace)");
     const Upsample u{disp, ih, iw, fh, fw, lin_ratio(ih, fh), lin_ratio(iw, fw)};
     const long long E = (long long)fh * fw;
-    const bool vec = E % 4 == 0 && aligned16(tail);
+    const bool vec = E % 4 == 0 && aligned_to(tail, 16);
     const long long groups = W_INTERP * E / (vec ? 4 : 1);
-    const int blocks = (int)std::min<long long>((groups + 255) / 256, FIT_MAX_BLOCKS);
+    const int blocks = blocks_for(groups, FIT_MAX_BLOCKS);
     double *partials = static_cast<double *>(ws);
     if (vec)
         EDV_LAUNCH(stitch_fit_kernel<4>, dim3(blocks), dim3(256), 0, stream, u, tail, partials);
@@ -213,9 +194,9 @@ int stitch_apply(const float *disp, int ih, int iw, const float *st, float *tail
         fade.keep[i] = (float)(1.0 - f);
         fade.take[i] = (float)f;
     }
-    const bool vec = E % 4 == 0 && aligned16(out_new) && (!tail || aligned16(tail));
+    const bool vec = E % 4 == 0 && aligned_to(out_new, 16) && (!tail || aligned_to(tail, 16));
     const long long groups = (st ? W_LEN - W_ALIGN : W_LEN) * E / (vec ? 4 : 1);
-    const int blocks = (int)std::min<long long>((groups + 255) / 256, 16384);
+    const int blocks = blocks_for(groups, 16384);
     if (vec)
         EDV_LAUNCH(stitch_apply_kernel<4>, dim3(blocks), dim3(256), 0, stream, u, st, tail, out_new, fade);
     else

@@ -6,7 +6,7 @@
 //                   and colour gathers are the scattered side: neighbouring voxels in x project to neighbouring pixels.
 //   tsdf_count      one workgroup per tile of TSDF_TILE voxels in linear order: the crossings of the tile (up to three a voxel, towards its +x, +y
 //                   and +z neighbour), counted by wave ballot and popcount, one 64-bit count per tile in the workspace; then the one-workgroup
-//                   exclusive scan of cloud_common.hpp, which leaves the total in total[0]
+//                   exclusive scan of compact_common.hpp, which leaves the total in total[0]
 //   tsdf_extract    the same tiles: the predicates again, the rank of every crossing inside its tile (voxel-major, axis-minor), the point in fp64,
 //                   and element stores of point g = tile offset + rank when g < capacity
 // One thread per voxel and a fixed frame order: no atomics anywhere, no workgroup waits for another, the same input gives the same bits on every
@@ -17,8 +17,9 @@
 
 #include "ops.hpp"
 
-#include "cloud_common.hpp"  // depth_value, kept, cloud_scan_kernel, check_selection: shared with pointcloud.hip
-#include "tsdf_common.hpp"   // TSDF_TILE, voxel_index, tiles_of, check_volume: shared with tsdf_mesh.hip
+#include "cloud_common.hpp"    // depth_value, kept, check_selection: shared with pointcloud.hip
+#include "compact_common.hpp"  // wave_count, tile_count_store, exclusive_scan_kernel, tile_ranks: shared with pointcloud.hip and tsdf_mesh.hip
+#include "tsdf_common.hpp"     // TSDF_TILE, voxel_index, tiles_of, check_volume: shared with tsdf_mesh.hip
 
 namespace edv {
 namespace {
@@ -106,7 +107,6 @@ __device__ __forceinline__ unsigned crossings(const TsdfVol &v, unsigned a, unsi
 
 // grid: tiles
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(TsdfVol v, float min_weight, unsigned voxels, u64 *__restrict__ counts) {
-    __shared__ unsigned red[TSDF_WAVES];
     unsigned c = 0;
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
@@ -114,62 +114,32 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(TsdfVol v, flo
         unsigned ix, iy, iz;
         float ta, tb[3];
         const unsigned bits = crossings(v, a, voxels, min_weight, ix, iy, iz, ta, tb);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c += (unsigned)__popcll(__ballot((bits >> k) & 1u));
+        c += wave_count<2>((unsigned)__popc(bits));
     }
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    if (lane == 0) red[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0;
-#pragma unroll
-        for (int w = 0; w < TSDF_WAVES; ++w) t += red[w];
-        counts[blockIdx.x] = t;
-    }
+    tile_count_store<TSDF_WAVES, 1>({c}, {counts}, blockIdx.x);
 }
 
 // grid: tiles
 template <bool COLOUR>
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_extract_kernel(TsdfVol v, float min_weight, unsigned voxels, const u64 *__restrict__ tile_offsets,
                                                                     float *__restrict__ points, uint8_t *__restrict__ colors, u64 capacity) {
-    __shared__ unsigned cnt[TSDF_ITERS][TSDF_WAVES];
     const u64 tile_base = tile_offsets[blockIdx.x];
     if (tile_base >= capacity) return;  // uniform over the workgroup: a tile that starts behind the capacity has nothing to write
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    const u64 below = (1ull << lane) - 1ull;
-    unsigned ix[TSDF_ITERS], iy[TSDF_ITERS], iz[TSDF_ITERS], bits[TSDF_ITERS], before[TSDF_ITERS];
+    unsigned ix[TSDF_ITERS], iy[TSDF_ITERS], iz[TSDF_ITERS], bits[TSDF_ITERS], c[TSDF_ITERS], rank[TSDF_ITERS];
     float ta[TSDF_ITERS], tb[TSDF_ITERS][3];
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
         const unsigned a = blockIdx.x * (unsigned)TSDF_TILE + it * TSDF_THREADS + threadIdx.x;
         bits[it] = crossings(v, a, voxels, min_weight, ix[it], iy[it], iz[it], ta[it], tb[it]);
-        unsigned in_wave = 0;
-        before[it] = 0;  // crossings of the lanes below this one: all three axes of a lower voxel come first
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const u64 ballot = __ballot((bits[it] >> k) & 1u);
-            in_wave += (unsigned)__popcll(ballot);
-            before[it] += (unsigned)__popcll(ballot & below);
-        }
-        if (lane == 0) cnt[it][wave] = in_wave;
+        c[it] = (unsigned)__popc(bits[it]);
     }
-    __syncthreads();
-    // rank of the first crossing of (iteration, wave): voxels are ordered by iteration, then wave, then lane
-    unsigned first[TSDF_ITERS] = {}, run = 0;
-#pragma unroll
-    for (int it = 0; it < TSDF_ITERS; ++it) {
-#pragma unroll
-        for (int w = 0; w < TSDF_WAVES; ++w) {
-            if (w == wave) first[it] = run;
-            run += cnt[it][w];
-        }
-    }
-    if (run == 0) return;
+    // the rank of the voxel's first crossing: all three axes of an earlier voxel come first
+    if (tile_ranks<TSDF_ITERS, TSDF_WAVES, 2>(c, rank) == 0) return;
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
         if (!bits[it]) continue;
         const unsigned a = blockIdx.x * (unsigned)TSDF_TILE + it * TSDF_THREADS + threadIdx.x;
-        u64 g = tile_base + first[it] + before[it];
+        u64 g = tile_base + rank[it];
         const double ctr[3] = {(double)ix[it] + 0.5, (double)iy[it] + 0.5, (double)iz[it] + 0.5};
         const unsigned hop[3] = {1u, (unsigned)v.nx, (unsigned)v.nx * (unsigned)v.ny};
 #pragma unroll
@@ -235,7 +205,7 @@ int tsdf_count(const TsdfVol &v, float min_weight, long long *total, void *ws, s
     u64 *counts = static_cast<u64 *>(ws);
     EDV_LAUNCH(tsdf_count_kernel, dim3((unsigned)tiles), dim3(TSDF_THREADS), 0, stream, v, min_weight, (unsigned)voxels, counts);
     EDV_LAUNCH_OK();
-    EDV_LAUNCH(cloud_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, counts, tiles, 0ll, total, 0ll);
+    EDV_LAUNCH(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, counts, tiles, 0ll, total, 0ll);
     EDV_LAUNCH_OK();
     return 0;
 }

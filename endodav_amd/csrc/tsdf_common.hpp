@@ -5,8 +5,6 @@
 
 #include "ops.hpp"
 
-#include "cloud_common.hpp"  // aligned_to
-
 namespace edv {
 namespace {
 

@@ -6,7 +6,7 @@
 //                  and its eight corners are observed)
 //   mesh_count     one workgroup per tile of TSDF_TILE voxels, from the flags alone: the 7-bit mask of the edges a -> a + off(d) that carry a
 //                  vertex (one byte per voxel) and the triangles of the voxel's cell; two 64-bit counts per tile, summed by wave ballot and
-//                  popcount over the bit planes of the per-voxel counts.  Then the one-workgroup scan of cloud_common.hpp, once per count array
+//                  popcount over the bit planes of the per-voxel counts.  Then the one-workgroup scan of compact_common.hpp, once per count array
 //   mesh_base      the same tiles: the rank of every voxel's first vertex inside its tile, and base[a] = tile offset + rank (u32 per voxel)
 //   mesh_vertex    one thread per voxel that owns vertices: position (fp64), normal and colour (fp32) of vertex base[a] + its rank in the mask
 //   mesh_triangle  the same tiles: the corner pattern of every valid cell again, the rank of its first triangle inside the tile, and per
@@ -19,8 +19,8 @@
 
 #include "ops.hpp"
 
-#include "cloud_common.hpp"  // cloud_scan_kernel, aligned_to
-#include "tsdf_common.hpp"   // TSDF_TILE, voxel_index, tiles_of, check_volume
+#include "compact_common.hpp"  // wave_count, tile_count_store, exclusive_scan_kernel, tile_ranks: shared with pointcloud.hip and tsdf.hip
+#include "tsdf_common.hpp"     // TSDF_TILE, voxel_index, tiles_of, check_volume
 
 namespace edv {
 namespace {
@@ -103,44 +103,6 @@ __device__ __forceinline__ unsigned triangles_of_case(unsigned m) {
     return inside <= 2 ? inside : 4 - inside;
 }
 
-// the sum over the wave of per-lane counts below 16, by ballot and popcount over their four bit planes; every lane of the wave calls it
-__device__ __forceinline__ unsigned wave_sum16(unsigned c) {
-    unsigned s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s += (unsigned)__popcll(__ballot((c >> k) & 1u)) << k;
-    return s;
-}
-
-// rank[it]: the sum of the counts (below 16 each) of the voxels of the tile before this thread's voxel of iteration `it`, the voxels ordered by
-// iteration, then wave, then lane.  Returns the tile's sum.  Every thread of the workgroup calls it.
-__device__ __forceinline__ unsigned tile_ranks(const unsigned (&c)[TSDF_ITERS], unsigned (&rank)[TSDF_ITERS], unsigned (&cnt)[TSDF_ITERS][TSDF_WAVES]) {
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    const u64 below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int it = 0; it < TSDF_ITERS; ++it) {
-        unsigned in_wave = 0;
-        rank[it] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const u64 ballot = __ballot((c[it] >> k) & 1u);
-            in_wave += (unsigned)__popcll(ballot) << k;
-            rank[it] += (unsigned)__popcll(ballot & below) << k;
-        }
-        if (lane == 0) cnt[it][wave] = in_wave;
-    }
-    __syncthreads();
-    unsigned run = 0;
-#pragma unroll
-    for (int it = 0; it < TSDF_ITERS; ++it) {
-#pragma unroll
-        for (int w = 0; w < TSDF_WAVES; ++w) {
-            if (w == wave) rank[it] += run;
-            run += cnt[it][w];
-        }
-    }
-    return run;
-}
-
 // grid: ceil(voxels / TSDF_THREADS)
 __global__ __launch_bounds__(TSDF_THREADS) void mesh_flags_kernel(TsdfVol v, float min_weight, unsigned voxels, uint8_t *__restrict__ flags) {
     const unsigned a = blockIdx.x * (unsigned)TSDF_THREADS + threadIdx.x;
@@ -197,7 +159,6 @@ __device__ __forceinline__ unsigned triangles_of_cell(unsigned pattern) {
 // grid: tiles
 __global__ __launch_bounds__(TSDF_THREADS) void mesh_count_kernel(TsdfVol v, unsigned voxels, const uint8_t *__restrict__ flags, uint8_t *__restrict__ mask,
                                                                   u64 *__restrict__ vertex_counts, u64 *__restrict__ triangle_counts) {
-    __shared__ unsigned red[2][TSDF_WAVES];
     unsigned nv = 0, nt = 0;
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
@@ -210,31 +171,22 @@ __global__ __launch_bounds__(TSDF_THREADS) void mesh_count_kernel(TsdfVol v, uns
             mask[a] = (uint8_t)vm;
             if (flags[a] & VALID) tc = triangles_of_cell(cell_pattern(v, flags, a));
         }
-        nv += wave_sum16((unsigned)__popc(vm));
-        nt += wave_sum16(tc);
+        nv += wave_count<4>((unsigned)__popc(vm));  // at most 7
+        nt += wave_count<4>(tc);                    // at most 12
     }
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    if (lane == 0) red[0][wave] = nv, red[1][wave] = nt;
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        unsigned t = 0;
-#pragma unroll
-        for (int w = 0; w < TSDF_WAVES; ++w) t += red[threadIdx.x][w];
-        (threadIdx.x == 0 ? vertex_counts : triangle_counts)[blockIdx.x] = t;
-    }
+    tile_count_store<TSDF_WAVES, 2>({nv, nt}, {vertex_counts, triangle_counts}, blockIdx.x);
 }
 
 // grid: tiles
 __global__ __launch_bounds__(TSDF_THREADS) void mesh_base_kernel(unsigned voxels, const uint8_t *__restrict__ mask, const u64 *__restrict__ vertex_offsets,
                                                                  unsigned *__restrict__ base) {
-    __shared__ unsigned cnt[TSDF_ITERS][TSDF_WAVES];
     unsigned c[TSDF_ITERS], rank[TSDF_ITERS];
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
         const unsigned a = blockIdx.x * (unsigned)TSDF_TILE + it * TSDF_THREADS + threadIdx.x;
         c[it] = a < voxels ? (unsigned)__popc((unsigned)mask[a]) : 0u;
     }
-    tile_ranks(c, rank, cnt);
+    tile_ranks<TSDF_ITERS, TSDF_WAVES, 4>(c, rank);
     const u64 tile_base = vertex_offsets[blockIdx.x];
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
@@ -303,7 +255,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void mesh_vertex_kernel(TsdfVol v, un
 __global__ __launch_bounds__(TSDF_THREADS) void mesh_triangle_kernel(TsdfVol v, unsigned voxels, const uint8_t *__restrict__ flags, const uint8_t *__restrict__ mask,
                                                                      const unsigned *__restrict__ base, const u64 *__restrict__ triangle_offsets,
                                                                      int *__restrict__ triangles, u64 capacity) {
-    __shared__ unsigned cnt[TSDF_ITERS][TSDF_WAVES];
     const u64 tile_base = triangle_offsets[blockIdx.x];
     if (tile_base >= capacity) return;  // uniform over the workgroup: a tile that starts behind the capacity has nothing to write
     unsigned pattern[TSDF_ITERS], c[TSDF_ITERS], rank[TSDF_ITERS];
@@ -316,7 +267,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void mesh_triangle_kernel(TsdfVol v, 
             c[it] = triangles_of_cell(pattern[it]);
         }
     }
-    if (tile_ranks(c, rank, cnt) == 0) return;
+    if (tile_ranks<TSDF_ITERS, TSDF_WAVES, 4>(c, rank) == 0) return;
 #pragma unroll
     for (int it = 0; it < TSDF_ITERS; ++it) {
         if (!c[it]) continue;
@@ -385,9 +336,9 @@ int tsdf_mesh_count(const TsdfVol &v, float min_weight, long long *totals, void 
     EDV_LAUNCH_OK();
     EDV_LAUNCH(mesh_count_kernel, per_tile, block, 0, stream, v, (unsigned)voxels, m.flags, m.mask, m.vertex_tiles, m.triangle_tiles);
     EDV_LAUNCH_OK();
-    EDV_LAUNCH(cloud_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, m.vertex_tiles, tiles, 0ll, totals, 0ll);
+    EDV_LAUNCH(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, m.vertex_tiles, tiles, 0ll, totals, 0ll);
     EDV_LAUNCH_OK();
-    EDV_LAUNCH(cloud_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, m.triangle_tiles, tiles, 0ll, totals + 1, 0ll);
+    EDV_LAUNCH(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, m.triangle_tiles, tiles, 0ll, totals + 1, 0ll);
     EDV_LAUNCH_OK();
     EDV_LAUNCH(mesh_base_kernel, per_tile, block, 0, stream, (unsigned)voxels, m.mask, m.vertex_tiles, m.base);
     EDV_LAUNCH_OK();

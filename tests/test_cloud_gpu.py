@@ -84,6 +84,20 @@ def test_lift_equals_the_host_mirror_under_every_option(cuda, source, per_frame,
         _same(cloud.lift(torch.from_numpy(x).to(cuda), spec, None if rgb is None else torch.from_numpy(rgb).to(cuda), output="device"), want)
 
 
+@pytest.mark.parametrize("clip_shape", [(4100, 1, 3), (2050, 1, cloud.TILE_PIXELS + 1)], ids=str)
+def test_lift_equals_the_host_mirror_beyond_one_round_of_the_scan(cuda, clip_shape):
+    """The one-workgroup scan takes 4096 tile counts a round and carries their total into the next: with one tile a frame the frames from
+    4096 on, with two tiles a frame (a full one and one pixel) the frames from 2048 on, take their offsets and tile bases from the carry."""
+    n, h, w = clip_shape
+    tiles_per_frame = -(-h * w // cloud.TILE_PIXELS)
+    assert n * tiles_per_frame > 4096
+    x, frames = cases.clip(clip_shape, "depth"), cases.colours(clip_shape)
+    spec = cases.spec_for(clip_shape)
+    want = cloud.lift_host(x, spec, frames)
+    assert 0 < len(want) < x.size and want.offsets[4096 // tiles_per_frame] < want.offsets[n]
+    _same(cloud.lift(x, spec, frames), want)
+
+
 # ---- b. keep patterns ---------------------------------------------------------------------------------------------------------------------------
 def _pattern(name, shape):
     """(depth, mask) of a "depth" clip whose kept set has the named form under near = 1e-3, far = 150."""

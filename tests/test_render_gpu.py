@@ -22,6 +22,9 @@ SHAPES = [(1, 1, 1), (3, 5, 7), (2, 6, 8), (4, 70, 98), (2, 130, 172)]
 KINDS = ["positive", "mixed", "negzero", "ties", "constant"]
 NORMS = ["video", "frame", "fixed", "quantile"]
 GUARD = 0xA5
+# the range kernels: every shape under every kind, then 65 frames, one more than a chunk of 64: the second chunk's minima, maxima and select
+# states live where the first chunk's did, and the select states must have been left cleared
+RANGE_CASES = [pytest.param(s, k, id=f"{s}-{k}") for s in SHAPES for k in KINDS] + [pytest.param((65, 5, 7), k, id=f"(65, 5, 7)-{k}") for k in ("mixed", "ties")]
 
 
 def _clip(shape, kind, seed=0):
@@ -60,8 +63,7 @@ def _range(lib, cuda, x, mode, ranks=(0, 0)):
 
 
 # ---- 1. the range kernels against numpy ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("shape", SHAPES, ids=str)
+@pytest.mark.parametrize("shape,kind", RANGE_CASES)
 def test_minimum_and_maximum_per_frame_and_per_video(lib, cuda, shape, kind):
     x = _clip(shape, kind)
     flat = x.reshape(shape[0], -1)
@@ -71,8 +73,7 @@ def test_minimum_and_maximum_per_frame_and_per_video(lib, cuda, shape, kind):
     assert np.array_equal(_bits(got), _bits(np.tile(np.array([x.min(), x.max()], np.float32), (shape[0], 1))))
 
 
-@pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("shape", SHAPES, ids=str)
+@pytest.mark.parametrize("shape,kind", RANGE_CASES)
 def test_order_statistics_per_frame(lib, cuda, shape, kind):
     x = _clip(shape, kind)
     m = shape[1] * shape[2]
