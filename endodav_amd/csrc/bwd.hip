@@ -250,14 +250,10 @@ __global__ __launch_bounds__(256) void lora_grad_finalize_kernel(const float *__
 }
 // dU[j] = sum_k dApT[k, j] A[j, k]: one workgroup per j
 __global__ __launch_bounds__(256) void lora_grad_u_kernel(const float *__restrict__ dApT, const float *__restrict__ A, float *__restrict__ dU, int nin, int r) {
-    __shared__ float red[4];
     const int j = blockIdx.x;
     float s = 0.f;
     for (int k = threadIdx.x; k < nin; k += 256) s += dApT[k * r + j] * A[(long long)j * nin + k];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) dU[j] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum_pairs_store({s}, dU + j);
 }
 
 // ---- bilinear, align_corners=True, backward as a deterministic gather (resample.hip bilinear_*) ---------------------------

@@ -135,7 +135,22 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-// the sum over a block of 256 threads of Q per-thread partials -> dst[0..Q): wave butterfly, then the four waves in order
+// The sum over a block of 256 threads of Q per-thread partials -> dst[0..Q), thread q < Q storing sum q: a wave butterfly, then the four per-wave
+// sums r0..r3.  The two helpers add them in DIFFERENT orders, each the one its callers' results were pinned with: the fp32 one in pairs,
+// (r0 + r1) + (r2 + r3); the fp64 one in wave order, ((r0 + r1) + r2) + r3.  dst may be LDS: the caller then syncs before it reads.
+template <int Q>
+__device__ __forceinline__ void block_sum_pairs_store(const float (&a)[Q], float *dst) {
+    __shared__ float red[4][Q];
+    float s[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = wave_sum(a[q]);
+    if ((threadIdx.x & 63) == 0) {  // the Q stores under one test: a test per store costs each caller a few instructions per partial
+#pragma unroll
+        for (int q = 0; q < Q; ++q) red[threadIdx.x >> 6][q] = s[q];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < Q) dst[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
 template <int Q>
 __device__ __forceinline__ void block_sum_store(double (&a)[Q], double *dst) {
     __shared__ double red[4][Q];

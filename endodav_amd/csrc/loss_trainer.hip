@@ -18,8 +18,9 @@
 // Structure per scale (P = H*W):
 //   bilinear x2              D = disp_s at the frame size (the geometry), D_c at the size of color(0, s) (the smoothness term)
 //   frame_sum x2, smooth     as loss.hip, at the size of color(0, s)
-//   warp_nb_kernel           x[fid][f][c][p]: the neighbour image sampled at the projection of every pixel (border padding)
-//   ssimw_kernel             32x32 tiles + halo in LDS: weighted SSIM + L1 against refined, the loss_transform term, dL/dx and dL/d refined (gather form)
+//   warp_nb_kernel           x[fid][f][c][p]: the neighbour image sampled at the projection of every pixel (border padding; loss_common.hpp warp_pixel)
+//   ssim_kernel<true>        (loss_common.hpp) 32x32 tiles + halo in LDS: weighted SSIM + L1 against refined, the loss_transform term, dL/dx and dL/d refined
+//                            (gather form)
 //   cvt_kernel               get_smooth_bright and dL/d transform_high
 //   dreproj_fwd / dflow_fwd  sums and counts of the two depth-consistency terms (their means need the counts before any gradient)
 //   geom_bwd_kernel          dL/dx through the sampling coordinates, the projection and the depth; the depth-reprojection term's gradient on the source
@@ -47,118 +48,8 @@ __global__ __launch_bounds__(256) void warp_nb_kernel(const float *__restrict__ 
     float *o = xw + (long long)f * 3 * P;
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long long)gridDim.x * 256) {
         const int y = (int)(p / W), x = (int)(p - (long long)y * W);
-        const float depth = 1.0f / (da + db * D[(long long)f * P + p]);
-        const Sample s = project_pixel(c, depth, x, y, H, W);
-        const float fx0 = floorf(s.ix), fy0 = floorf(s.iy);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx = s.ix - fx0, wy = s.iy - fy0;
-        const bool xin = x0 + 1 < W, yin = y0 + 1 < H;
-        const float w00 = (1.f - wx) * (1.f - wy), w01 = wx * (1.f - wy), w10 = (1.f - wx) * wy, w11 = wx * wy;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float *sc = src + ch * P + (long long)y0 * W + x0;
-            float v = sc[0] * w00;
-            if (xin) v += sc[1] * w01;
-            if (yin) v += sc[W] * w10;
-            if (xin && yin) v += sc[W + 1] * w11;
-            o[ch * P + p] = v;
-        }
+        warp_pixel(c, D[(long long)f * P + p], x, y, src, o + p, P, H, W, da, db);
     }
-}
-
-// ---- weighted SSIM + L1 against refined, + the loss_transform term ---------------------------------------------------------------------------------
-// One workgroup = (tile, channel, frame).  w_q = w_rep m_q / M: the per-pixel weight of the reprojection term; w_tr m_p / M that of |refined - registration_0|.
-// SSIM(q) depends on x AND y through the window means: A, B, C = w_q * dSSIM/d(mu_x, E[x^2], E[xy]), A2 = w_q dSSIM/d mu_y (B serves E[y^2] too: the
-// expression is symmetric in sigma_x + sigma_y).  part[(f * 3 + ch) * tiles + tile] = {reprojection partial, transform partial}.
-__global__ __launch_bounds__(256) void ssimw_kernel(const float *__restrict__ xw, const float *__restrict__ refined, const float *__restrict__ reg0,
-                                                    const float *__restrict__ mask, const float *__restrict__ msum, float *__restrict__ gx, float *__restrict__ gy,
-                                                    float *__restrict__ part, int H, int W, int tiles_x, float w_rep, float w_tr) {
-    __shared__ float sx[TI * TI], sy[TI * TI], cA[TC * TC], cA2[TC * TC], cB[TC * TC], cC[TC * TC];
-    __shared__ float red[2][4];
-    const long long P = (long long)H * W;
-    const int tile = blockIdx.x, ch = blockIdx.y, f = blockIdx.z;
-    const int ty0 = (tile / tiles_x) * TS, tx0 = (tile % tiles_x) * TS;
-    const float *xs = xw + ((long long)f * 3 + ch) * P, *ys = refined + ((long long)f * 3 + ch) * P, *mf = mask + (long long)f * P;
-    const float inv_m = 1.0f / msum[0];
-    const float w_ssim = w_rep * 0.85f / 3.0f * inv_m, w_l1 = w_rep * 0.15f / 3.0f * inv_m, w_t = w_tr / 3.0f * inv_m;
-    for (int i = threadIdx.x; i < TI * TI; i += 256) {
-        const int r = i / TI, c = i - r * TI;
-        int y = reflect1(ty0 - 2 + r, H), x = reflect1(tx0 - 2 + c, W);
-        y = y < 0 ? 0 : (y >= H ? H - 1 : y);
-        x = x < 0 ? 0 : (x >= W ? W - 1 : x);
-        sx[i] = xs[(long long)y * W + x];
-        sy[i] = ys[(long long)y * W + x];
-    }
-    __syncthreads();
-    float lrep = 0.f, ltr = 0.f;
-    for (int i = threadIdx.x; i < TC * TC; i += 256) {
-        const int r = i / TC, c = i - r * TC;
-        const int qy = ty0 - 1 + r, qx = tx0 - 1 + c;
-        float A = 0.f, A2 = 0.f, B = 0.f, C = 0.f;
-        if (qy >= 0 && qy < H && qx >= 0 && qx < W) {
-            const float wq = w_ssim * mf[(long long)qy * W + qx];
-            float s_x = 0.f, s_y = 0.f, s_xx = 0.f, s_yy = 0.f, s_xy = 0.f;
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const float a = sx[(r + dy) * TI + c + dx], b = sy[(r + dy) * TI + c + dx];
-                    s_x += a; s_y += b; s_xx += a * a; s_yy += b * b; s_xy += a * b;
-                }
-            const float mu_x = s_x / 9.0f, mu_y = s_y / 9.0f;
-            const float sig_x = s_xx / 9.0f - mu_x * mu_x, sig_y = s_yy / 9.0f - mu_y * mu_y, sig_xy = s_xy / 9.0f - mu_x * mu_y;
-            const float n1 = 2.0f * mu_x * mu_y + SSIM_C1, n2 = 2.0f * sig_xy + SSIM_C2;
-            const float d1 = mu_x * mu_x + mu_y * mu_y + SSIM_C1, d2 = sig_x + sig_y + SSIM_C2;
-            const float n = n1 * n2, d = d1 * d2;
-            const float raw = (1.0f - n / d) / 2.0f;
-            const bool inner = r >= 1 && r <= TS && c >= 1 && c <= TS;
-            if (inner) lrep += wq * fminf(1.0f, fmaxf(raw, 0.0f));
-            if (raw >= 0.0f && raw <= 1.0f) {
-                const float k = -0.5f * wq / (d * d);
-                A = k * (2.0f * mu_y * (n2 - n1) * d - n * 2.0f * mu_x * (d2 - d1));
-                A2 = k * (2.0f * mu_x * (n2 - n1) * d - n * 2.0f * mu_y * (d2 - d1));
-                B = k * (-n * d1);
-                C = k * (2.0f * n1 * d);
-            }
-        }
-        cA[i] = A; cA2[i] = A2; cB[i] = B; cC[i] = C;
-    }
-    __syncthreads();
-    float *gox = gx + ((long long)f * 3 + ch) * P, *goy = gy ? gy + ((long long)f * 3 + ch) * P : nullptr;
-    const float *rg = reg0 + ((long long)f * 3 + ch) * P;
-    for (int i = threadIdx.x; i < TS * TS; i += 256) {
-        const int r = i / TS, c = i - r * TS;
-        const int py = ty0 + r, px = tx0 + c;
-        if (py >= H || px >= W) continue;
-        float SA = 0.f, SA2 = 0.f, SB = 0.f, SC = 0.f;
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy) {
-            const float my = 1.0f + ((dy == 1 && py == H - 2) || (dy == -1 && py == 1) ? 1.0f : 0.0f);
-#pragma unroll
-            for (int dx = -1; dx <= 1; ++dx) {
-                const float m = my * (1.0f + ((dx == 1 && px == W - 2) || (dx == -1 && px == 1) ? 1.0f : 0.0f));
-                const int j = (r + 1 + dy) * TC + c + 1 + dx;
-                SA += m * cA[j]; SA2 += m * cA2[j]; SB += m * cB[j]; SC += m * cC[j];
-            }
-        }
-        const float xv = sx[(r + 2) * TI + c + 2], yv = sy[(r + 2) * TI + c + 2];
-        const float mp = mf[(long long)py * W + px];
-        const float diff = yv - xv;
-        const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-        lrep += w_l1 * mp * fabsf(diff);
-        gox[(long long)py * W + px] = (SA + 2.0f * xv * SB + yv * SC) / 9.0f - w_l1 * mp * sgn;
-        const float dt = yv - rg[(long long)py * W + px];
-        ltr += w_t * mp * fabsf(dt);
-        if (goy) goy[(long long)py * W + px] = (SA2 + 2.0f * yv * SB + xv * SC) / 9.0f + w_l1 * mp * sgn + w_t * mp * (dt > 0.f ? 1.f : (dt < 0.f ? -1.f : 0.f));
-    }
-    const float v[2] = {lrep, ltr};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float s = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) part[(((long long)f * 3 + ch) * gridDim.x + tile) * 2 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
 // ---- get_smooth_bright (utils/layers.py:239-264) and dL/d transform_high ---------------------------------------------------------------------------
@@ -166,7 +57,6 @@ __global__ __launch_bounds__(256) void ssimw_kernel(const float *__restrict__ xw
 // The loss terms are counted at the pair's first pixel; the gradient of t_c(p) gathers the four pairs p belongs to.  part[f][block] = partial sum.
 __global__ __launch_bounds__(256) void cvt_kernel(const float *__restrict__ tr, const float *__restrict__ color0, const float *__restrict__ reg, const float *__restrict__ mask,
                                                   const float *__restrict__ msum, float *__restrict__ gtr, float *__restrict__ part, int H, int W, float w_cvt) {
-    __shared__ float red[4];
     const int f = blockIdx.y;
     const long long P = (long long)H * W;
     const float *t = tr + (long long)f * 3 * P, *c0 = color0 + (long long)f * 3 * P, *rg = reg + (long long)f * 3 * P, *m = mask + (long long)f * P;
@@ -219,16 +109,12 @@ __global__ __launch_bounds__(256) void cvt_kernel(const float *__restrict__ tr, 
             for (int ch = 0; ch < 3; ++ch) gtr[((long long)f * 3 + ch) * P + p] = g[ch];
         }
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(long long)f * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum_pairs_store({acc}, part + (long long)f * gridDim.x + blockIdx.x);
 }
 
 // sums of the mask the normalisations need: out[0] = sum m, out[1] = sum m[:, :, :, :-1], out[2] = sum m[:, :, :-1, :]   (MASK_BLOCKS workgroups per frame, then one wave)
 constexpr int MASK_BLOCKS = 32;
 __global__ __launch_bounds__(256) void mask_sums_kernel(const float *__restrict__ mask, float *__restrict__ part, int H, int W) {
-    __shared__ float red[3][4];
     const int f = blockIdx.y;
     const long long P = (long long)H * W;
     const float *m = mask + (long long)f * P;
@@ -240,14 +126,7 @@ __global__ __launch_bounds__(256) void mask_sums_kernel(const float *__restrict_
         if (x + 1 < W) bx += v;
         if (y + 1 < H) by += v;
     }
-    const float v[3] = {a, bx, by};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float s = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) part[((long long)f * MASK_BLOCKS + blockIdx.x) * 3 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    block_sum_pairs_store({a, bx, by}, part + ((long long)f * MASK_BLOCKS + blockIdx.x) * 3);
 }
 __global__ __launch_bounds__(64) void mask_sums_finish_kernel(const float *__restrict__ part, float *__restrict__ out, int n) {
     float a = 0.f, b = 0.f, c = 0.f;
@@ -323,7 +202,6 @@ __device__ __forceinline__ void project_unclipped(const Cam &c, float depth, int
 // part[((nb * N + f) * blocks + b) * 2] = {sum |Z - sampled| over the mask, count}
 __global__ __launch_bounds__(256) void dreproj_fwd_kernel(const float *__restrict__ D, const Cam *__restrict__ cams, float *__restrict__ part, int N, int H, int W, float da,
                                                           float db) {
-    __shared__ float red[2][4];
     const long long P = (long long)H * W;
     const int f = blockIdx.y, nb = blockIdx.z, j = nb ? f + 1 : f - 1;
     float sum = 0.f, cnt = 0.f;
@@ -343,14 +221,7 @@ __global__ __launch_bounds__(256) void dreproj_fwd_kernel(const float *__restric
             }
         }
     }
-    const float v[2] = {sum, cnt};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float t = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) part[(((long long)nb * N + f) * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    block_sum_pairs_store({sum, cnt}, part + (((long long)nb * N + f) * gridDim.x + blockIdx.x) * 2);
 }
 
 // SpatialTransformer (utils/layers.py:409-426): sample at pixel + flow; flow channel 0 is the row displacement
@@ -361,7 +232,6 @@ __device__ __forceinline__ void flow_coords(const float *__restrict__ fl, long l
 }
 __global__ __launch_bounds__(256) void dflow_fwd_kernel(const float *__restrict__ D, const float *__restrict__ flow, int nb, float *__restrict__ part, int N, int H, int W,
                                                         float da, float db) {
-    __shared__ float red[2][4];
     const long long P = (long long)H * W;
     const int f = blockIdx.y, j = nb ? f + 1 : f - 1;  // origin frame f, forward frame j
     float sum = 0.f, cnt = 0.f;
@@ -378,31 +248,17 @@ __global__ __launch_bounds__(256) void dflow_fwd_kernel(const float *__restrict_
             }
         }
     }
-    const float v[2] = {sum, cnt};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float t = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) part[(((long long)nb * N + f) * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    block_sum_pairs_store({sum, cnt}, part + (((long long)nb * N + f) * gridDim.x + blockIdx.x) * 2);
 }
 // tot[nb * 2 + {0, 1}] = {sum, count} over every frame and block (one workgroup, fixed order)
 __global__ __launch_bounds__(256) void pair_sums_kernel(const float *__restrict__ part, long long n_per_nb, float *__restrict__ tot) {
-    __shared__ float red[4][4];
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     for (int nb = 0; nb < 2; ++nb)
         for (long long i = threadIdx.x; i < n_per_nb; i += 256) {
             v[nb * 2] += part[((long long)nb * n_per_nb + i) * 2];
             v[nb * 2 + 1] += part[((long long)nb * n_per_nb + i) * 2 + 1];
         }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float t = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) tot[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+    block_sum_pairs_store(v, tot);
 }
 
 // the flow term's gradient: -sign / count into the forward frame's depth at p, +sign w_k / count into the origin frame's depth at the four corners
@@ -525,7 +381,7 @@ __global__ __launch_bounds__(256) void geom_bwd_kernel(const float *__restrict__
                 for (int b = 0; b < 3; ++b) acc[24 + a * 3 + b] += gr[a] * pix[b];
         }
     }
-    if (POSE) {
+    if (POSE) {  // block_sum_pairs_store's order, kept by hand: through the helper this kernel loses speed or its gradients move (profiles/loss_shared_notes.txt)
 #pragma unroll
         for (int k = 0; k < 33; ++k) {
             const float t = wave_sum(acc[k]);
@@ -608,8 +464,8 @@ struct FinishArgs {
     float w_sm, inv_nx, inv_ny, w_dr, w_df;
 };
 __global__ __launch_bounds__(256) void finish_scale_kernel(FinishArgs a, float *__restrict__ S, float *__restrict__ losses, int s) {
-    __shared__ float red[5][4];
-    float rep = 0.f, tr = 0.f, cvt = 0.f, tx = 0.f, ty = 0.f;
+    __shared__ float t[5];
+    float rep = 0.f, tr = 0.f, cvt = 0.f, tx, ty;
     for (int nb = 0; nb < 2; ++nb) {
         for (long long i = threadIdx.x; i < a.n_ssim; i += 256) {
             rep += a.ssim_part[nb][i * 2];
@@ -617,25 +473,10 @@ __global__ __launch_bounds__(256) void finish_scale_kernel(FinishArgs a, float *
         }
         for (int i = threadIdx.x; i < a.n_cvt; i += 256) cvt += a.cvt_part[nb][i];
     }
-    for (int i = threadIdx.x; i < a.N * a.sm_blocks; i += 256) {
-        tx += a.sm_part[(long long)i * 3];
-        ty += a.sm_part[(long long)i * 3 + 1];
-    }
-    for (int f = threadIdx.x; f < a.N; f += 256) {
-        float t = 0.f;
-        for (int b = 0; b < a.sm_blocks; ++b) t += a.sm_part[((long long)f * a.sm_blocks + b) * 3 + 2];
-        S[f] = t;
-    }
-    const float v[5] = {rep, tr, cvt, tx, ty};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const float t = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = t;
-    }
+    smooth_part_sums(a.sm_part, a.sm_blocks, a.N, S, tx, ty);
+    block_sum_pairs_store({rep, tr, cvt, tx, ty}, t);
     __syncthreads();
     if (threadIdx.x == 0) {
-        float t[5];
-        for (int k = 0; k < 5; ++k) t[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
         // every weight (1/2 per neighbour pair, the options' factors, 1 / 2^s) is already inside the partial sums EXCEPT the mean over the four scales,
         // so that losses[s * 7 + k] are the trainer's per-scale entries (trainer :960-966)
         const float l_rep = t[0], l_tr = t[1], l_cvt = t[2], l_sm = a.w_sm * (t[3] * a.inv_nx + t[4] * a.inv_ny);
@@ -657,33 +498,31 @@ struct TLWs {  // carve-up of the caller's workspace (floats)
 constexpr int SM_BLOCKS = 64, CVT_BLOCKS = 64, PAIR_BLOCKS = 64, POSE_BLOCKS = 128;
 TLWs tl_layout(int N, int H, int W) {
     const size_t P = (size_t)H * W;
-    const size_t tiles = (size_t)((H + TS - 1) / TS) * ((W + TS - 1) / TS);
-    auto up = [](size_t n) { return (n + 3) & ~(size_t)3; };
     TLWs w;
-    size_t o = 0;
-    w.cams = o; o += up(2 * (size_t)N * (sizeof(Cam) / sizeof(float)));
-    w.msum = o; o += up(2 * 4);
-    w.mpart = o; o += up((size_t)N * MASK_BLOCKS * 3);
-    w.D = o; o += up((size_t)N * P);
-    w.Dc = o; o += up((size_t)N * P);
-    w.mean = o; o += up(N);
-    w.S = o; o += up(N);
-    w.sum_part = o; o += up((size_t)N * SUM_PARTS);
-    w.sm_part = o; o += up((size_t)N * SM_BLOCKS * 3);
-    for (int nb = 0; nb < 2; ++nb) { w.ssim_part[nb] = o; o += up((size_t)N * 3 * tiles * 2); }
-    for (int nb = 0; nb < 2; ++nb) { w.cvt_part[nb] = o; o += up((size_t)N * CVT_BLOCKS); }
-    w.pair_part = o; o += up(2 * (size_t)N * PAIR_BLOCKS * 2);
-    w.drp_tot = o; o += 4;
-    w.dfl_tot = o; o += 4;
-    w.gsm = o; o += up((size_t)N * P);
-    w.gDc = o; o += up((size_t)N * P);
-    w.gD = o; o += up((size_t)N * P);
-    w.gdg = o; o += up((size_t)N * P);
-    w.gdep = o; o += up((size_t)N * P);
-    w.xw = o; o += up(2 * (size_t)N * 3 * P);
-    w.gx = o; o += up(2 * (size_t)N * 3 * P);
-    w.pose_part = o; o += up((size_t)N * POSE_BLOCKS * 33);
-    w.total = o;
+    Carve c;
+    w.cams = c.take(2 * (size_t)N * (sizeof(Cam) / sizeof(float)));
+    w.msum = c.take(2 * 4);
+    w.mpart = c.take((size_t)N * MASK_BLOCKS * 3);
+    w.D = c.take((size_t)N * P);
+    w.Dc = c.take((size_t)N * P);
+    w.mean = c.take(N);
+    w.S = c.take(N);
+    w.sum_part = c.take((size_t)N * SUM_PARTS);
+    w.sm_part = c.take((size_t)N * SM_BLOCKS * 3);
+    for (int nb = 0; nb < 2; ++nb) w.ssim_part[nb] = c.take((size_t)N * 3 * ssim_tiles(H, W) * 2);
+    for (int nb = 0; nb < 2; ++nb) w.cvt_part[nb] = c.take((size_t)N * CVT_BLOCKS);
+    w.pair_part = c.take(2 * (size_t)N * PAIR_BLOCKS * 2);
+    w.drp_tot = c.take(4);
+    w.dfl_tot = c.take(4);
+    w.gsm = c.take((size_t)N * P);
+    w.gDc = c.take((size_t)N * P);
+    w.gD = c.take((size_t)N * P);
+    w.gdg = c.take((size_t)N * P);
+    w.gdep = c.take((size_t)N * P);
+    w.xw = c.take(2 * (size_t)N * 3 * P);
+    w.gx = c.take(2 * (size_t)N * 3 * P);
+    w.pose_part = c.take((size_t)N * POSE_BLOCKS * 33);
+    w.total = c.o;
     return w;
 }
 
@@ -705,9 +544,9 @@ int trainer_loss(const TrainerLossIn &in, int N, int H, int W, const TrainerLoss
     float *msum = ws + L.msum, *mpart = ws + L.mpart, *Dbuf = ws + L.D, *Dcbuf = ws + L.Dc, *mean = ws + L.mean, *S = ws + L.S, *sum_part = ws + L.sum_part,
           *sm_part = ws + L.sm_part, *pair_part = ws + L.pair_part, *drp_tot = ws + L.drp_tot, *dfl_tot = ws + L.dfl_tot, *gsm = ws + L.gsm, *gDc = ws + L.gDc, *gD = ws + L.gD,
           *gdg = ws + L.gdg, *gdep = ws + L.gdep, *xw = ws + L.xw, *gx = ws + L.gx, *pose_part = ws + L.pose_part;
-    const float da = (float)(1.0 / (double)wt.max_depth), db = (float)(1.0 / (double)wt.min_depth - 1.0 / (double)wt.max_depth);
-    const int tiles_x = (W + TS - 1) / TS, tiles = tiles_x * ((H + TS - 1) / TS);
-    const int pix_blocks = (int)((P + 255) / 256 < 1024 ? (P + 255) / 256 : 1024);
+    const auto [da, db] = depth_coef(wt.min_depth, wt.max_depth);
+    const int tiles_x = ceil_div(W, TS), tiles = (int)ssim_tiles(H, W);
+    const int pix_blocks = blocks_for(P, 1024);
     const float tw = wt.tune_temporal ? 1.0f : 0.0f;
     const bool do_dr = tw * wt.depth_reproj != 0.f, do_df = tw * wt.depth_flow != 0.f;
     const bool pose = g.K || g.invK || g.T[0] || g.T[1];
@@ -758,8 +597,8 @@ int trainer_loss(const TrainerLossIn &in, int N, int H, int W, const TrainerLoss
             EDV_LAUNCH(warp_nb_kernel, dim3(pix_blocks, N), dim3(256), 0, st, D, in.color_nb[nb], cams, nb, xw_nb, H, W, da, db);
             EDV_LAUNCH_OK();
             // per-scale weights: rep / 2, tc tr / 2 (trainer :953-954); the 1/4 of the mean over scales multiplies every GRADIENT below (0.25 * ...)
-            EDV_LAUNCH(ssimw_kernel, dim3(tiles, 3, N), dim3(256), 0, st, xw_nb, in.refined[s][nb], in.registration[0][nb], in.mask[nb], msum + nb * 4, gx_nb,
-                               g.refined[s][nb], ws + L.ssim_part[nb], H, W, tiles_x, 0.5f, 0.5f * wt.transform_constraint);
+            EDV_LAUNCH(ssim_kernel<true>, dim3(tiles, 3, N), dim3(256), 0, st, xw_nb, in.refined[s][nb], in.registration[0][nb], in.mask[nb], msum + nb * 4, gx_nb,
+                               g.refined[s][nb], ws + L.ssim_part[nb], nullptr, N, H, W, tiles_x, 0.5f, 0.5f * wt.transform_constraint);
             EDV_LAUNCH_OK();
             EDV_LAUNCH(cvt_kernel, dim3(CVT_BLOCKS, N), dim3(256), 0, st, in.transform[s][nb], in.color[0], in.registration[s][nb], in.mask[nb], msum + nb * 4,
                                g.transform[s][nb], ws + L.cvt_part[nb], H, W, 0.5f * wt.transform_smoothness);
