@@ -349,6 +349,12 @@ int edv_tsdf_mesh_extract(const edv_tsdf_volume *vol, float /*min_weight*/, cons
                              triangle_capacity, (hipStream_t)stream);
 }
 
+int edv_tsdf_raycast(const edv_tsdf_volume *vol, const double *cams_dev, int32_t views, int32_t h, int32_t w, double near, double step, int32_t steps,
+                     float min_weight, float *depth_dev, float *normals_dev, uint8_t *colors_dev, void *stream) {
+    EDV_CHECK(vol, "null volume");
+    return tsdf_raycast(tsdf_vol(*vol), cams_dev, views, h, w, near, step, steps, min_weight, depth_dev, normals_dev, colors_dev, (hipStream_t)stream);
+}
+
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,
                    size_t workspace_bytes, void *stream) {

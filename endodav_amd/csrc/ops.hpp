@@ -193,6 +193,11 @@ size_t tsdf_mesh_workspace(int nx, int ny, int nz);  // bytes: 6 per voxel and 1
 int tsdf_mesh_count(const TsdfVol &v, float min_weight, long long *totals, void *ws, size_t ws_bytes, hipStream_t stream);
 int tsdf_mesh_extract(const TsdfVol &v, const void *ws, size_t ws_bytes, float *vertices, float *normals, uint8_t *colors, long long vertex_capacity,
                       int *triangles, long long triangle_capacity, hipStream_t stream);
+// views of the volume (tsdf_raycast.hip): one thread per pixel of cams [views][21] doubles (the cloud's Kinv, R, t) marches `steps` samples
+// z_k = near + k * step, stops at the first change from outside to inside between two valid samples and writes depth [views, h, w], and where
+// not null normals [views, h, w, 3] and colors [views, h, w, 3]; a miss writes zeros
+int tsdf_raycast(const TsdfVol &v, const double *cams, int views, int h, int w, double near, double step, int steps, float min_weight, float *depth,
+                 float *normals, uint8_t *colors, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -1,4 +1,5 @@
-// What tsdf.hip and tsdf_mesh.hip share: the tile of the extraction kernels, the index of a voxel and the checks of an edv_tsdf_volume.
+// What tsdf.hip, tsdf_mesh.hip and tsdf_raycast.hip share: the tile of the extraction kernels, the index of a voxel, the hop of a cell corner, the
+// gradient of a voxel and the checks of an edv_tsdf_volume.
 // Everything here is internal to the translation unit that includes it.
 #pragma once
 #include <cmath>
@@ -15,6 +16,19 @@ constexpr int TSDF_TILE = TSDF_THREADS * TSDF_ITERS;  // voxels per workgroup of
 __device__ __forceinline__ void voxel_index(const TsdfVol &v, unsigned a, unsigned &ix, unsigned &iy, unsigned &iz) {
     const unsigned r = a / (unsigned)v.nx;
     ix = a - r * (unsigned)v.nx, iz = r / (unsigned)v.ny, iy = r - iz * (unsigned)v.ny;
+}
+
+// the linear hop of offset d = (d & 1, d >> 1 & 1, d >> 2 & 1)
+__device__ __forceinline__ unsigned hop_of(const TsdfVol &v, unsigned d) {
+    return (d & 1u) + ((d >> 1) & 1u) * (unsigned)v.nx + ((d >> 2) & 1u) * (unsigned)v.nx * (unsigned)v.ny;
+}
+
+// g_k = tsdf[i_k -> min(i_k + 1, n_k - 1)] - tsdf[i_k -> max(i_k - 1, 0)]: every index stays in the grid
+__device__ __forceinline__ void gradient(const TsdfVol &v, unsigned a, unsigned ix, unsigned iy, unsigned iz, float (&g)[3]) {
+    const unsigned hx = 1u, hy = (unsigned)v.nx, hz = (unsigned)v.nx * (unsigned)v.ny;
+    g[0] = v.tsdf[ix + 1 < (unsigned)v.nx ? a + hx : a] - v.tsdf[ix > 0 ? a - hx : a];
+    g[1] = v.tsdf[iy + 1 < (unsigned)v.ny ? a + hy : a] - v.tsdf[iy > 0 ? a - hy : a];
+    g[2] = v.tsdf[iz + 1 < (unsigned)v.nz ? a + hz : a] - v.tsdf[iz > 0 ? a - hz : a];
 }
 
 inline long long tiles_of(long long voxels) { return (voxels + TSDF_TILE - 1) / TSDF_TILE; }

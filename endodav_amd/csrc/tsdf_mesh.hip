@@ -20,7 +20,7 @@
 #include "ops.hpp"
 
 #include "compact_common.hpp"  // wave_count, tile_count_store, exclusive_scan_kernel, tile_ranks: shared with pointcloud.hip and tsdf.hip
-#include "tsdf_common.hpp"     // TSDF_TILE, voxel_index, tiles_of, check_volume
+#include "tsdf_common.hpp"     // TSDF_TILE, voxel_index, hop_of, gradient, tiles_of, check_volume
 
 namespace edv {
 namespace {
@@ -87,11 +87,6 @@ constexpr MeshTable make_mesh_table() {
 }
 
 __constant__ MeshTable MESH_TABLE = make_mesh_table();
-
-// the linear hop of offset d = (d & 1, d >> 1 & 1, d >> 2 & 1)
-__device__ __forceinline__ unsigned hop_of(const TsdfVol &v, unsigned d) {
-    return (d & 1u) + ((d >> 1) & 1u) * (unsigned)v.nx + ((d >> 2) & 1u) * (unsigned)v.nx * (unsigned)v.ny;
-}
 
 // the case mask of tetrahedron ti under the cell's corner pattern (bit c: corner c inside)
 __device__ __forceinline__ unsigned tet_case(unsigned pattern, int ti) {
@@ -193,14 +188,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void mesh_base_kernel(unsigned voxels
         const unsigned a = blockIdx.x * (unsigned)TSDF_TILE + it * TSDF_THREADS + threadIdx.x;
         if (a < voxels) base[a] = (unsigned)(tile_base + rank[it]);
     }
-}
-
-// g_k = tsdf[i_k -> min(i_k + 1, n_k - 1)] - tsdf[i_k -> max(i_k - 1, 0)]: every index stays in the grid
-__device__ __forceinline__ void gradient(const TsdfVol &v, unsigned a, unsigned ix, unsigned iy, unsigned iz, float (&g)[3]) {
-    const unsigned hx = 1u, hy = (unsigned)v.nx, hz = (unsigned)v.nx * (unsigned)v.ny;
-    g[0] = v.tsdf[ix + 1 < (unsigned)v.nx ? a + hx : a] - v.tsdf[ix > 0 ? a - hx : a];
-    g[1] = v.tsdf[iy + 1 < (unsigned)v.ny ? a + hy : a] - v.tsdf[iy > 0 ? a - hy : a];
-    g[2] = v.tsdf[iz + 1 < (unsigned)v.nz ? a + hz : a] - v.tsdf[iz > 0 ? a - hz : a];
 }
 
 // grid: ceil(voxels / TSDF_THREADS).  normals and colors may be null

@@ -846,17 +846,21 @@ class endodav(nn.Module):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             return cloud.lift(depth, spec, frames=rgb, output=output)
 
-    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host", surface="points"):
+    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host", surface="points", views=None):
         """A video as one coloured surface (not in the reference): ``infer_video_depth(frames, stitch="device", output="device")``, then every
         frame integrated into the TSDF ``volume`` (a ``fusion.Volume``) with ``spec`` (a ``cloud.Cloud`` with ``step=1``: intrinsics, poses,
         depth rule and mask) and the uint8 frames, uploaded once, as the colours, then the zero crossings of the volume between voxels of
         weight >= ``min_weight`` (``fusion.Tsdf``).  The float32 video never reaches the host; only the surface points do.
         Returns a ``cloud.PointCloud`` with ``offsets = [0, total]``: numpy arrays, or with ``output="device"`` tensors on the GPU.
-        ``surface="mesh"`` returns the triangle mesh of the volume instead, a ``fusion.Mesh`` with normals and colours (``fusion.Tsdf.mesh``)."""
+        ``surface="mesh"`` returns the triangle mesh of the volume instead, a ``fusion.Mesh`` with normals and colours (``fusion.Tsdf.mesh``).
+        ``surface="views"`` returns the volume as the cameras ``views`` (a ``fusion.Views``) see it, a ``fusion.Raycast`` of depth, normal and
+        colour maps (``fusion.Tsdf.raycast``)."""
         from . import cloud, fusion
 
-        if surface not in ("points", "mesh"):
-            raise ValueError(f"surface must be 'points' or 'mesh', got {surface!r}")
+        if surface not in ("points", "mesh", "views"):
+            raise ValueError(f"surface must be 'points', 'mesh' or 'views', got {surface!r}")
+        if (surface == "views") != (views is not None):
+            raise ValueError("surface='views' takes views (a fusion.Views) and the other surfaces take none")
         if not isinstance(spec, cloud.Cloud):
             raise ValueError(f"spec must be a cloud.Cloud, got {type(spec).__name__}")
         if not isinstance(volume, fusion.Volume):
@@ -864,12 +868,17 @@ class endodav(nn.Module):
         if int(spec.step) != 1:  # refused before the video is inferred, not after
             raise ValueError(f"fusion samples the full-resolution clip: the Cloud must have step 1, got {spec.step}")
         fusion._check_surface(min_weight, output)
+        if surface == "views":
+            fusion._check_raycast(views, min_weight, True, output)
+            views.march(volume.voxel)
         frames = np.ascontiguousarray(frames)
         depth = self.infer_video_depth(frames, input_size=input_size, device=device, stitch="device", output="device")
         with torch.cuda.device(depth.device):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             tsdf = fusion.Tsdf(volume, coloured=True, device=depth.device)
             tsdf.integrate(depth, spec, frames=rgb)
+            if surface == "views":
+                return tsdf.raycast(views, min_weight=min_weight, output=output)
             if surface == "mesh":
                 return tsdf.mesh(min_weight=min_weight, output=output)
             return tsdf.surface(min_weight=min_weight, output=output)

@@ -1,5 +1,5 @@
 """Surface fusion on the GPU (opt-in): a depth video with its poses integrated into one truncated signed distance (TSDF) volume, and the zero
-crossings of that volume as one coloured point list or as one coloured, oriented, indexed triangle mesh.  Not in the reference, whose ``3d_reconstruction`` clouds concatenate every frame's points:
+crossings of that volume as one coloured point list, as one coloured, oriented, indexed triangle mesh, or as depth, normal and colour maps seen from given cameras.  Not in the reference, whose ``3d_reconstruction`` clouds concatenate every frame's points:
 a thousand re-observations of the same tissue, each frame's depth noise a shell of its own.  Here every voxel averages what the frames saw.
 
 ``Volume`` says where the voxels are; ``Tsdf`` owns the arrays on the GPU (``edv_tsdf_integrate`` / ``edv_tsdf_count`` / ``edv_tsdf_extract``,
@@ -54,13 +54,41 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
             Degenerate cases stay: tsdf_a == 0 gives t = 0, so several vertices coincide and some triangles have zero area; the topology is
             unaffected and nothing is filtered.
 
-What is not built: hashed or sparse volumes, and pose estimation; poses are inputs, as for the cloud."""
+  views     the volume as cameras see it (``Views``, ``Tsdf.raycast`` / ``TsdfHost.raycast`` -> ``Raycast``; ``edv_tsdf_raycast``): one thread per
+            pixel marches its ray in equal steps of the cloud's depth and stops where the interpolated distance turns negative between two
+            neighbouring valid samples.  Every operation is rounded on its own; no division in the march.
+            setup     the cameras are ``Cloud(K=..., pose=...).cams(m)``: 21 doubles a view, Kinv, R and t, formed once on the host and handed
+                      to both implementations; inv = 1.0 / voxel in float64, formed once on the host;
+                      steps = floor((far - near) / step) + 1 in float64 in Python, at most ``MAX_STEPS``; step = the voxel unless given
+            float64   per pixel (x, y) of view f:  u = x + 0.5, v = y + 0.5;  l_i = (Kinv[i,0]*u + Kinv[i,1]*v) + Kinv[i,2];
+                      r_i = (R[i,0]*l_0 + R[i,1]*l_1) + R[i,2]*l_2 (the cloud's ray: a point at depth z is t + r*z);
+                      o_i = (t_i - origin_i) * inv - 0.5 and d_i = r_i * inv: the ray in voxel-centre coordinates
+            sample    at parameter z, float64:  g_i = o_i + d_i * z;  inside when 0 <= g_i <= n_i - 1 for i = x, y, z (NaN fails);
+                      c_i = min(max(int(g_i), 0), n_i - 2);  f_i = float32(g_i - float64(c_i));  valid when inside and the eight voxels
+                      c + off(0..7) all have weight >= min_weight
+            float32   along x: a00 = v000 + f_x*(v100 - v000), and a10, a01, a11 likewise for (y+1), (z+1), (y+1, z+1);
+                      along y: b0 = a00 + f_y*(a10 - a00), b1 = a01 + f_y*(a11 - a01);  along z: s = b0 + f_z*(b1 - b0)
+            march     k = 0 .. steps-1 with z_k = near + float64(k) * step (not accumulated).  Sample k not valid: the previous sample is
+                      forgotten.  Valid and not s < 0 (0 and -0 are outside, as everywhere here): (s, k) is remembered as the previous
+                      sample.  Valid, s < 0 and sample k-1 remembered: a hit.  Valid and s < 0 otherwise: the ray ends as a miss (it entered
+                      the surface from unobserved space, or started inside).  The steps run out: a miss.
+            hit       float32 t = s_prev / (s_prev - s), the divisor positive;  float64 z* = z_{k-1} + float64(t) * step;
+                      depth = float32(z*).  (c, f) again from z* by the formulas above (the clamp keeps them defined whatever the rounding);
+                      weights are not consulted again, as the mesh's gradient takes stored values.
+            float32   normal: the gradients g_k of the eight corners (the mesh's, no division), each component interpolated in the order
+                      above;  (n_x*n_x + n_y*n_y) + n_z*n_z, sqrt, n_k / len if len > 0, otherwise (0, 0, 0): exactly the mesh's.
+                      colour: the eight stored colours interpolated per channel in the same order;  uint8(min(255, max(0, floor(c + 0.5))))
+            miss      depth 0, normal (0, 0, 0), colour (0, 0, 0).  Every pixel of every output is written exactly once, hit or miss.  A
+                      volume with some n_i = 1 has no cell: every pixel is a miss.
+            The depth is the cloud's: ``cloud.lift(depth, Cloud(K, pose, source="depth"))`` puts the hits back in the world.
+
+What is not built: hashed or sparse volumes, shading, free-space skipping, and pose estimation; poses are inputs, as for the cloud."""
 from __future__ import annotations
 
 import ctypes as C
 import itertools
 import math
-from dataclasses import dataclass
+from dataclasses import KW_ONLY, dataclass
 
 import numpy as np
 import torch
@@ -223,6 +251,94 @@ def _check_mesh(min_weight, normals, output):
     return _check_surface(min_weight, output)
 
 
+MAX_STEPS = 65536  # samples along a ray: the bound of the kernel's loop
+
+
+@dataclass(frozen=True, eq=False)
+class Views:
+    """The cameras that look at a volume (module docstring, "views"), and how their rays are sampled."""
+    K: object                                # intrinsics [3, 3] or [m, 3, 3]
+    pose: object = None                      # T_world_camera [3, 4] / [4, 4] or one per view; None = identity
+    _: KW_ONLY
+    size: object                             # (h, w) of every view
+    near: float                              # the first sample's depth
+    far: float                               # no sample lies beyond it
+    step: float = None                       # depth between two samples; None = the volume's voxel
+
+    def __post_init__(self):
+        spec = Cloud(K=self.K, pose=self.pose)                   # finite, well-formed, K invertible
+        counts = (spec.K.shape[0], spec.pose.shape[0])
+        if min(counts) != 1 and counts[0] != counts[1]:
+            raise ValueError(f"K holds {counts[0]} matrices and pose {counts[1]}: equal counts, or one of them a single matrix")
+        object.__setattr__(self, "K", spec.K)
+        object.__setattr__(self, "pose", spec.pose)
+        size = tuple(self.size) if np.ndim(self.size) == 1 else ()
+        if len(size) != 2 or any(isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 1 for d in size):
+            raise ValueError(f"size must be two integers (h, w) >= 1, got {self.size!r}")
+        object.__setattr__(self, "size", tuple(int(d) for d in size))
+        for name in ("near", "far"):
+            x = getattr(self, name)
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.floating, np.integer)) or not math.isfinite(x):
+                raise ValueError(f"{name} must be a finite number, got {x!r}")
+            object.__setattr__(self, name, float(x))
+        if not 0.0 <= self.near < self.far:
+            raise ValueError(f"need 0 <= near < far, got near={self.near!r}, far={self.far!r}")
+        if self.step is not None:
+            if not _positive(self.step):
+                raise ValueError(f"step must be finite and positive, got {self.step!r}")
+            object.__setattr__(self, "step", float(self.step))
+            self.march(self.step)
+        if self.count * self.size[0] * self.size[1] >= 2 ** 31:
+            raise ValueError(f"the views hold fewer than 2^31 pixels, got {self.count} x {self.size[0]} x {self.size[1]}")
+
+    @property
+    def count(self) -> int:
+        return max(self.K.shape[0], self.pose.shape[0])
+
+    def march(self, voxel: float):
+        """(step, steps): the depth between two samples (the volume's ``voxel`` unless the views set one) and the number of samples,
+        floor((far - near) / step) + 1 in float64."""
+        step = float(voxel) if self.step is None else self.step
+        steps = math.floor((self.far - self.near) / step) + 1
+        if steps > MAX_STEPS:
+            raise ValueError(f"step {step!r} gives {steps} samples between near and far, at most {MAX_STEPS}")
+        return step, steps
+
+    def cams(self) -> np.ndarray:
+        """float64 [m, 21]: ``cloud.Cloud.cams`` of these cameras, one row per view."""
+        m = self.count
+        return np.ascontiguousarray(np.broadcast_to(Cloud(K=self.K, pose=self.pose).cams(m), (m, 21)))
+
+
+@dataclass(eq=False)
+class Raycast:
+    """The fused surface as the views see it: numpy arrays, or tensors on the GPU."""
+    depth: object                            # float32 [m, h, w], the cloud's depth of the surface along each pixel's ray; 0 where it finds none
+    normals: object                          # float32 [m, h, w, 3] unit vectors in the world frame towards free space, or None
+    colors: object                           # uint8 [m, h, w, 3], or None
+
+
+def _check_raycast(views, min_weight, normals, output):
+    if not isinstance(views, Views):
+        raise ValueError(f"views must be a fusion.Views, got {type(views).__name__}")
+    return _check_mesh(min_weight, normals, output)
+
+
+def _cell(g, dims):
+    """The cells [3, p] int64 that hold the points g [3, p] (voxel-centre coordinates) and the float32 positions inside them."""
+    c = np.stack([np.minimum(np.maximum(g[i].astype(np.int64), 0), dims[i] - 2) for i in range(3)])
+    return c, (g - c.astype(np.float64)).astype(np.float32)
+
+
+def _trilinear(q, f):
+    """q [8, p, ...] float32 at the corners c = x | y << 1 | z << 2 and f [3, p]: along x, then y, then z, every operation rounded on its own."""
+    fx, fy, fz = (f[i].reshape(f[i].shape + (1,) * (q.ndim - 2)) for i in range(3))
+    a00, a10 = q[0] + fx * (q[1] - q[0]), q[2] + fx * (q[3] - q[2])
+    a01, a11 = q[4] + fx * (q[5] - q[4]), q[6] + fx * (q[7] - q[6])
+    b0, b1 = a00 + fy * (a10 - a00), a01 + fy * (a11 - a01)
+    return b0 + fz * (b1 - b0)
+
+
 def _staged(a: np.ndarray, dev: torch.device) -> torch.Tensor:
     """A host array on the GPU through pinned memory, ordered on the current stream: the host does not wait for the stream's earlier work."""
     a = np.ascontiguousarray(a)
@@ -252,6 +368,12 @@ class TsdfHost:
         nx, ny, nz = self.volume.dims
         a = np.arange(self.volume.voxels, dtype=np.int64)
         return a % nx, (a // nx) % ny, a // (nx * ny)
+
+    def _gradients(self):
+        """float32 [voxels, 3]: g_k = tsdf[i_k -> min(i_k + 1, n_k - 1)] - tsdf[i_k -> max(i_k - 1, 0)] of every voxel."""
+        nx, ny, nz = self.volume.dims
+        return np.stack([np.take(self.tsdf, np.minimum(np.arange(n) + 1, n - 1), axis=ax) - np.take(self.tsdf, np.maximum(np.arange(n) - 1, 0), axis=ax)
+                         for ax, n in ((2, nx), (1, ny), (0, nz))], axis=-1).reshape(-1, 3)
 
     def integrate(self, depth, spec: Cloud, frames=None) -> None:
         depth = np.asarray(depth)
@@ -368,8 +490,7 @@ class TsdfHost:
                 vertices[:, j] = (origin[j] + np.where((d >> j) & 1 == 1, ctr + frac.astype(np.float64), ctr) * voxel).astype(np.float32)
             unit = None
             if normals:
-                g = np.stack([np.take(self.tsdf, np.minimum(np.arange(n) + 1, n - 1), axis=ax) - np.take(self.tsdf, np.maximum(np.arange(n) - 1, 0), axis=ax)
-                              for ax, n in ((2, nx), (1, ny), (0, nz))], axis=-1).reshape(-1, 3)
+                g = self._gradients()
                 n = g[a] + frac[:, None] * (g[b] - g[a])
                 length = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
                 unit = np.where((length > 0)[:, None], n / length[:, None], np.float32(0.0)).astype(np.float32)
@@ -389,9 +510,79 @@ class TsdfHost:
         return Mesh(vertices, unit, colors, triangles)
 
 
+    def raycast(self, views: Views, min_weight: float = 1.0, normals: bool = True, output: str = "host") -> Raycast:
+        """The volume as ``views`` see it (module docstring, "views"), vectorised over the pixels of a view: a loop over the steps on the
+        rays still marching."""
+        mw = _check_raycast(views, min_weight, normals, output)
+        if output != "host":
+            raise ValueError("the host mirror has no device output")
+        vol = self.volume
+        dims = nx, ny, nz = vol.dims
+        step, steps = views.march(vol.voxel)
+        cams, near, (h, w), m = views.cams(), views.near, views.size, views.count
+        origin, inv = np.float64(vol.origin), 1.0 / vol.voxel
+        depth = np.zeros((m, h * w), np.float32)
+        unit = np.zeros((m, h * w, 3), np.float32) if normals else None
+        colors = np.zeros((m, h * w, 3), np.uint8) if self.color is not None else None
+        shaped = Raycast(depth.reshape(m, h, w), None if unit is None else unit.reshape(m, h, w, 3), None if colors is None else colors.reshape(m, h, w, 3))
+        if min(dims) < 2:                                                # no cell: every pixel is a miss
+            return shaped
+        t, wt = self.tsdf.reshape(-1), self.weight.reshape(-1)
+        hop = np.array([dx + nx * (dy + ny * dz) for dx, dy, dz in OFFSETS], np.int64)
+        u = np.broadcast_to((np.arange(w, dtype=np.float64) + 0.5)[None, :], (h, w)).reshape(-1)
+        v = np.broadcast_to((np.arange(h, dtype=np.float64) + 0.5)[:, None], (h, w)).reshape(-1)
+        top = np.array(dims, np.float64)[:, None] - 1.0
+        grads = self._gradients() if normals else None
+        for f in range(m):
+            kinv, rot, pos = cams[f, :9].reshape(3, 3), cams[f, 9:18].reshape(3, 3), cams[f, 18:]
+            with np.errstate(all="ignore"):
+                l = [(kinv[i, 0] * u + kinv[i, 1] * v) + kinv[i, 2] for i in range(3)]
+                r = [(rot[i, 0] * l[0] + rot[i, 1] * l[1]) + rot[i, 2] * l[2] for i in range(3)]
+                o = np.stack([np.full(h * w, (pos[i] - origin[i]) * inv - 0.5) for i in range(3)])
+                d = np.stack([r[i] * inv for i in range(3)])
+                alive = np.arange(h * w)                                 # the rays still marching
+                have, sp = np.zeros(h * w, bool), np.zeros(h * w, np.float32)
+                hits, hit_k, hit_t = [], [], []
+                for k in range(steps):
+                    if alive.size == 0:
+                        break
+                    z = near + float(k) * step
+                    g = o[:, alive] + d[:, alive] * z
+                    ok = ((g >= 0.0) & (g <= top)).all(axis=0)           # inside; NaN fails
+                    c, fr = _cell(g[:, ok], dims)
+                    a = c[0] + nx * (c[1] + ny * c[2])
+                    valid = (wt[a[None, :] + hop[:, None]] >= mw).all(axis=0)
+                    ok[ok] = valid
+                    s = _trilinear(t[a[None, valid] + hop[:, None]], fr[:, valid])
+                    rays = alive[ok]
+                    inside = s < 0                                       # 0 and -0 count as outside
+                    hit = inside & have[rays]
+                    hits.append(rays[hit])
+                    hit_k.append(np.full(int(hit.sum()), k - 1, np.int64))
+                    hit_t.append(sp[rays[hit]] / (sp[rays[hit]] - s[hit]))
+                    have[alive] = False                                  # a sample that is not valid forgets the previous one
+                    have[rays[~inside]], sp[rays[~inside]] = True, s[~inside]
+                    done = np.zeros(alive.size, bool)
+                    done[ok] = inside                                    # a hit, or a miss that entered the surface unseen
+                    alive = alive[~done]
+                rays, frac = np.concatenate(hits), np.concatenate(hit_t)
+                zs = (near + np.concatenate(hit_k).astype(np.float64) * step) + frac.astype(np.float64) * step
+                depth[f, rays] = zs.astype(np.float32)
+                c, fr = _cell(o[:, rays] + d[:, rays] * zs, dims)        # the clamp keeps the cell in the grid whatever the rounding
+                corners = (c[0] + nx * (c[1] + ny * c[2]))[None, :] + hop[:, None]
+                if normals:
+                    n = _trilinear(grads[corners], fr)
+                    length = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+                    unit[f, rays] = np.where((length > 0)[:, None], n / length[:, None], np.float32(0.0)).astype(np.float32)
+                if colors is not None:
+                    col = _trilinear(self.color.reshape(-1, 3)[corners], fr)
+                    colors[f, rays] = np.minimum(np.float32(255.0), np.maximum(np.float32(0.0), np.floor(col + np.float32(0.5)))).astype(np.uint8)
+        return shaped
+
+
 class Tsdf:
-    """A TSDF volume on the GPU.  ``integrate`` folds clips into it, ``surface`` reads its zero crossings; both run on the caller's current
-    stream.  ``arrays`` and the tensors ``tsdf``, ``weight`` and ``color`` show the state."""
+    """A TSDF volume on the GPU.  ``integrate`` folds clips into it, ``surface`` and ``mesh`` read its zero crossings, ``raycast`` views it from
+    cameras; all run on the caller's current stream.  ``arrays`` and the tensors ``tsdf``, ``weight`` and ``color`` show the state."""
 
     def __init__(self, volume: Volume, coloured: bool = True, device="cuda"):
         if not isinstance(volume, Volume):
@@ -516,6 +707,33 @@ class Tsdf:
                     h.copy_(o, non_blocking=True)
             stream.synchronize()
             return Mesh(*(None if h is None else h.numpy() for h in host))
+
+
+    def raycast(self, views: Views, min_weight: float = 1.0, normals: bool = True, output: str = "host") -> Raycast:
+        """The volume as ``views`` see it (module docstring, "views"): a depth map, and unless ``normals=False`` a normal map, and for a coloured
+        volume a colour image, per view.  One launch on the caller's current stream, the cameras staged through pinned memory.  Returns a
+        ``Raycast`` of numpy arrays, or with ``output="device"`` of tensors on the GPU ordered on the caller's stream; the host waits only for
+        the copy of a host result."""
+        mw = float(_check_raycast(views, min_weight, normals, output))
+        step, steps = views.march(self.volume.voxel)
+        m, (h, w) = views.count, views.size
+        dev = self.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            cams_d = _staged(views.cams(), dev)
+            shapes = [((m, h, w), torch.float32), ((m, h, w, 3), torch.float32) if normals else None, ((m, h, w, 3), torch.uint8) if self.coloured else None]
+            out = [None if s is None else torch.empty(s[0], dtype=s[1], device=dev) for s in shapes]
+            vol = self.struct()
+            _lib.check(self._lib.edv_tsdf_raycast(C.byref(vol), cams_d.data_ptr(), m, h, w, views.near, step, steps, mw, out[0].data_ptr(), _lib.ptr(out[1]),
+                                                  _lib.ptr(out[2]), self._stream()), "edv_tsdf_raycast")
+            if output == "device":
+                return Raycast(*out)
+            host = [None if o is None else torch.empty(o.shape, dtype=o.dtype, pin_memory=True) for o in out]
+            for hst, o in zip(host, out):
+                if hst is not None:
+                    hst.copy_(o, non_blocking=True)
+            stream.synchronize()
+            return Raycast(*(None if hst is None else hst.numpy() for hst in host))
 
 
 def _face_dtype():

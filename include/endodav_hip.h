@@ -481,6 +481,45 @@ int edv_tsdf_mesh_extract(const edv_tsdf_volume *vol, float min_weight, const vo
                           float *normals_dev, uint8_t *colors_dev, int64_t vertex_capacity, int32_t *triangles_dev, int64_t triangle_capacity,
                           void *stream);
 
+/* ---- views of the fused surface (fusion.Tsdf.raycast, model.video_surface(surface="views")) ----
+ * An additive entry point: the ABI version stays as it is.  Every pixel of every view marches its ray through the volume in equal steps of
+ * depth and stops where the interpolated distance changes from outside to inside between two neighbouring valid samples.  The volume is only
+ * read.  fusion.TsdfHost.raycast is the numpy mirror, bit for bit.  Every operation below is rounded on its own (no contraction, no fast math).
+ * cams_dev [views][21] doubles: per view Kinv [3][3], R [3][3] and t [3] of the point cloud (cloud.Cloud.cams), formed once on the host.
+ * inv = 1.0 / voxel in fp64, formed once on the host.  steps = floor((far - near) / step) + 1 is the caller's, at most 65536.
+ * Per pixel (x, y) of view f, in fp64:
+ *     u = x + 0.5, v = y + 0.5;  l_i = (Kinv[i][0]*u + Kinv[i][1]*v) + Kinv[i][2]
+ *     r_i = (R[i][0]*l_0 + R[i][1]*l_1) + R[i][2]*l_2                   (the cloud's ray: a point at depth z is t + r*z)
+ *     o_i = (t_i - origin[i]) * inv - 0.5;  d_i = r_i * inv             (the ray in voxel-centre coordinates)
+ * The sample at parameter z:
+ *     fp64  g_i = o_i + d_i * z;  inside <=> 0 <= g_i <= n_i - 1 for i = x, y, z (NaN fails)
+ *           c_i = min(max((int)g_i, 0), n_i - 2);  f_i = (float)(g_i - (double)c_i)
+ *           valid <=> inside and the eight voxels c + off(0..7) all have weight >= min_weight
+ *     fp32  along x: a00 = v000 + f_x*(v100 - v000), and a10, a01, a11 likewise for (y+1), (z+1), (y+1, z+1)
+ *           along y: b0 = a00 + f_y*(a10 - a00), b1 = a01 + f_y*(a11 - a01);  along z: s = b0 + f_z*(b1 - b0)
+ * The march, k = 0 .. steps-1 with z_k = near + (double)k * step in fp64 (not accumulated):
+ *     sample k not valid: the previous sample is forgotten;  valid and not s < 0 (0 and -0 are outside, as everywhere here): (s, k) is
+ *     remembered as the previous sample;  valid, s < 0 and sample k-1 remembered: a hit;  valid and s < 0 otherwise: the ray ends as a miss
+ *     (it entered the surface from unobserved space, or started inside);  the steps run out: a miss.
+ * The hit:
+ *     fp32  t = s_prev / (s_prev - s)                                   (the divisor is positive)
+ *     fp64  z* = z_{k-1} + (double)t * step;  depth = (float)z*
+ *     (c, f) from z* by the formulas above (the clamp keeps them defined whatever the rounding); weights are not consulted again
+ *     fp32  normal: the gradients of the eight corners (the mesh's, no division), each component interpolated in the order above;
+ *           s = (n_x*n_x + n_y*n_y) + n_z*n_z;  len = sqrt(s), correctly rounded;  n_k / len if len > 0 and (0, 0, 0) otherwise
+ *           colour: the eight stored colours interpolated per channel in the same order; (uint8) min(255, max(0, floor(c + 0.5)))
+ * A miss writes depth 0, normal (0, 0, 0) and colour (0, 0, 0).  A volume with some n_i = 1 has no cell: every pixel is a miss.
+ * depth_dev [views][h][w] fp32; normals_dev [views][h][w][3] fp32 or NULL; colors_dev [views][h][w][3] uint8 or NULL (not NULL only for a
+ * coloured volume).  Every pixel of every output given is written exactly once, hit or miss, so nothing needs clearing.
+ * One launch, one thread per pixel, a workgroup a 16 x 16 pixel tile.  Each ray skips the samples a slab test shows to lie outside the box
+ * of voxel centres; the test inside the loop stays authoritative, so only samples the rule calls not valid are skipped.
+ * No atomics and no waiting between workgroups: the same input gives the same bits on every call.
+ * A null volume, cameras or depth pointer, the volume refusals above, cameras not 8-byte and depth or normals not 4-byte aligned, views, h or
+ * w below 1, views*h*w >= 2^31, a step that is not finite and positive, a near that is not finite, steps outside 1..65536, and colours asked
+ * of a volume that has none return non-zero and launch nothing. */
+int edv_tsdf_raycast(const edv_tsdf_volume *vol, const double *cams_dev, int32_t views, int32_t h, int32_t w, double near, double step, int32_t steps,
+                     float min_weight, float *depth_dev, float *normals_dev, uint8_t *colors_dev, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
