@@ -3,8 +3,9 @@
 //
 //   stage 1  colsum_stage1   one launch for up to CS_MAX_JOBS jobs: job j is cut into `parts` row chunks x ceil(N / CW) column blocks,
 //                            one workgroup each.  CW = the next power of two >= N (at most 256); the 256 / CW row lanes of a workgroup
-//                            walk the chunk's rows with stride 256 / CW (four independent accumulators each), then lane 0 of every column
-//                            adds the row lanes in index order and writes one partial row into the job's slab region [parts, N].
+//                            walk the chunk's rows with stride 256 / CW (four independent accumulators each), then the row lanes of every
+//                            column are added in pairs in fp64 (a halving tree in LDS), rounded once, and one partial row goes into the
+//                            job's slab region [parts, N].
 //   stage 2  colsum_stage2   one launch for up to CS_MAX_OUTS outputs: output o adds `rows` consecutive partial rows of the slab in index
 //                            order (several jobs that feed one tensor -- pretrained.norm.bias is reached from four taps -- lie back to
 //                            back), multiplies by scale[n] and writes or accumulates dst[n].
@@ -37,7 +38,7 @@ struct Stage2Args {
 };
 
 __global__ __launch_bounds__(256) void colsum_stage1(const Stage1Args a) {
-    __shared__ float red[256];
+    __shared__ double red[256];
     const int j = find_item(a.wg_begin, a.n, blockIdx.x);
     const ColsumJob &jb = a.job[j];
     const int local = blockIdx.x - a.wg_begin[j];
@@ -60,13 +61,15 @@ __global__ __launch_bounds__(256) void colsum_stage1(const Stage1Args a) {
         }
         for (; r < r1; r += rl_n) s0 += src[jb.map(r) * jb.ld];
     }
-    red[threadIdx.x] = (s0 + s1) + (s2 + s3);
+    red[threadIdx.x] = ((double)s0 + (double)s1) + ((double)s2 + (double)s3);
     __syncthreads();
-    if (rl == 0 && col < jb.N) {
-        float t = red[cc];
-        for (int k = 1; k < rl_n; ++k) t += red[k * cw + cc];
-        jb.slab[(long long)part * jb.N + col] = t;
+    // The row lanes of a column (threads cc, cc + cw, ...) are joined in pairs, halving, in fp64, and rounded to fp32 once.  One lane adding
+    // the other 255 in fp32 in sequence (N = 1) lost 6 u of sum |P| on rows with a mean, seventeen times torch's own sum; an fp32 tree still 1.5 u.
+    for (int h = rl_n >> 1; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h * cw) red[threadIdx.x] += red[threadIdx.x + h * cw];
+        __syncthreads();
     }
+    if (rl == 0 && col < jb.N) jb.slab[(long long)part * jb.N + col] = (float)red[cc];
 }
 
 __global__ __launch_bounds__(256) void colsum_stage2(const Stage2Args a) {

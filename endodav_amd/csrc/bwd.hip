@@ -810,6 +810,8 @@ int lora_grad_finalize(const float *dBp, const float *dApT, const float *A, cons
     return 0;
 }
 
+// The + 64 is spare for alignment: lora_grads rounds the t and u regions [M, r] up to a multiple of 4 floats each (at most 6 floats,
+// when r = 1 and M is odd), so that every region behind them starts 16-byte aligned for the f32x4 loads of skinny_xwt_kernel.
 size_t lora_grads_workspace(long long M, int nin, int nout, int r) {
     const int nmax = nin > nout ? nin : nout;
     return (size_t)2 * M * r + (size_t)r * (nin + nout) + tall_tn_workspace(nmax, r) + (size_t)r * (nin + nout) + 64;
@@ -821,7 +823,8 @@ int lora_grads(const float *X, int ldx, const float *G, int ldg, long long M, in
                const float *V, float s, const float *gamma, float *ws, size_t ws_floats, float *dA, float *dB, float *dU, float *dV, hipStream_t st) {
     EDV_CHECK(X && G && A && Bm && ws, "null operand");
     EDV_CHECK(ws_floats >= lora_grads_workspace(M, nin, nout, r), "workspace too small (lora_grads_workspace)");
-    float *t = ws, *u = t + M * r, *Aeff = u + M * r, *BgT = Aeff + (size_t)r * nin;
+    const size_t mr4 = ((size_t)M * r + 3) / 4 * 4;  // t and u padded to whole float4s: Aeff, BgT, part, dBp and dApT stay 16-byte aligned
+    float *t = ws, *u = t + mr4, *Aeff = u + mr4, *BgT = Aeff + (size_t)r * nin;
     float *part = BgT + (size_t)r * nout;
     float *dBp = part + tall_tn_workspace(nin > nout ? nin : nout, r), *dApT = dBp + (size_t)r * nout;
     const int nf = r * (nin > nout ? nin : nout);
