@@ -158,6 +158,10 @@ SIGNATURES = {
     "edv_tsdf_mesh_extract": (C.c_int, [C.c_void_p, _f32, _fp, C.c_size_t, _fp, _fp, _fp, _i64, _fp, _i64, C.c_void_p]),
     # views of the volume (additive, ABI stays 15): cams [views][21] doubles on the device; normals and colours may be NULL
     "edv_tsdf_raycast": (C.c_int, [C.c_void_p, _fp, _i32, _i32, _i32, _f64, _f64, _i32, _f32, _fp, _fp, _fp, C.c_void_p]),
+    # camera tracking against the volume (additive, ABI stays 15): a CloudSelection, the two cameras as host doubles (21 and 39), one raycast view
+    "edv_icp_tile_pixels": (_i32, []),
+    "edv_icp_workspace": (C.c_size_t, [_i32, _i32, _i32]),
+    "edv_icp_sums": (C.c_int, [C.c_void_p, _i64, C.POINTER(_f64), C.POINTER(_f64), _fp, _fp, _i32, _i32, _f64, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

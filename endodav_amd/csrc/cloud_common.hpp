@@ -1,4 +1,5 @@
-// What pointcloud.hip and tsdf.hip share: the depth rule and keep predicate of a CloudSel (edv_cloud_selection) and its checks.
+// What pointcloud.hip, tsdf.hip and tsdf_track.hip share: the depth rule and keep predicate of a CloudSel (edv_cloud_selection), the source pixel
+// of an output pixel of its subsampled grid, and its checks.
 // Everything here is internal to the translation unit that includes it.
 // Contraction is off from here to the end of that unit: every fp32 and fp64 operation is numpy's, in the order written.
 #pragma once
@@ -20,6 +21,14 @@ __device__ __forceinline__ float depth_value(const CloudSel &s, float x) {
 __device__ __forceinline__ bool kept(const CloudSel &s, float x, unsigned m, float &z) {
     z = depth_value(s, x);
     return m != 0 && z > s.near_z && z < s.far_z;
+}
+
+// output pixel q = oy * ow + ox of the subsampled grid -> the source pixel that holds the grid position ((ox + 0.5) * step, (oy + 0.5) * step)
+__device__ __forceinline__ int source_pixel(const CloudSel &s, int ow, unsigned q, int &ox, int &oy) {
+    oy = (int)(q / (unsigned)ow), ox = (int)(q - (unsigned)oy * (unsigned)ow);
+    const long long sy = min((long long)oy * s.step + s.step / 2, (long long)s.h - 1);
+    const long long sx = min((long long)ox * s.step + s.step / 2, (long long)s.w - 1);
+    return (int)(sy * s.w + sx);  // h * w < 2^31
 }
 
 inline int check_selection(const CloudSel &s) {

@@ -198,6 +198,13 @@ int tsdf_mesh_extract(const TsdfVol &v, const void *ws, size_t ws_bytes, float *
 // not null normals [views, h, w, 3] and colors [views, h, w, 3]; a miss writes zeros
 int tsdf_raycast(const TsdfVol &v, const double *cams, int views, int h, int w, double near, double step, int steps, float min_weight, float *depth,
                  float *normals, uint8_t *colors, hipStream_t stream);
+// camera tracking against the volume (tsdf_track.hip): the 29 sums of one point-to-plane ICP step between frame `frame` of the selection, lifted
+// through live_cam (host, 21 doubles: the cloud's Kinv, R, t of the estimate), and one view of tsdf_raycast seen through model_cam (host, 39
+// doubles: that view's 21, then the 18 of tsdf_integrate); per-tile sums in the workspace, then their sum in tile order in sums [29]
+int icp_tile_pixels();  // output pixels per workgroup, 29 * 8 workspace bytes each
+size_t icp_workspace(int h, int w, int step);  // bytes; 0 for a shape the call refuses
+int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
+             double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -27,14 +27,6 @@ constexpr int CLOUD_THREADS = 256, CLOUD_WAVES = CLOUD_THREADS / WAVE;
 constexpr int CLOUD_ITERS = 8;
 constexpr int CLOUD_TILE = CLOUD_THREADS * CLOUD_ITERS;  // output pixels per workgroup: the one constant behind cloud_tile_pixels()
 
-// output pixel q = oy * ow + ox of the subsampled grid -> the source pixel that holds the grid position ((ox + 0.5) * step, (oy + 0.5) * step)
-__device__ __forceinline__ int source_pixel(const CloudSel &s, int ow, unsigned q, int &ox, int &oy) {
-    oy = (int)(q / (unsigned)ow), ox = (int)(q - (unsigned)oy * (unsigned)ow);
-    const long long sy = min((long long)oy * s.step + s.step / 2, (long long)s.h - 1);
-    const long long sx = min((long long)ox * s.step + s.step / 2, (long long)s.w - 1);
-    return (int)(sy * s.w + sx);  // h * w < 2^31
-}
-
 // grid (tiles per frame, frames).  UNIT: step == 1, where the source pixel is the output pixel
 template <bool UNIT>
 __global__ __launch_bounds__(CLOUD_THREADS) void cloud_count_kernel(CloudSel s, int ow, unsigned grid_pixels, u64 *__restrict__ counts) {

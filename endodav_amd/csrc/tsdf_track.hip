@@ -1,0 +1,175 @@
+#pragma clang fp contract(off)
+// Camera tracking against the fused surface: the normal equations of one point-to-plane ICP step.  A live depth frame, lifted through the
+// current estimate of its camera, is associated projectively with one view of tsdf_raycast.hip (the model's depth and normal maps seen from the
+// previous pose), and the 6 x 6 system of the twist about the live camera centre is summed over the pairs.  The rule is stated once, in
+// include/endodav_hip.h; fusion.icp_sums_host is the mirror, bit for bit.
+//   icp_tile   one workgroup per tile of ICP_TILE output pixels of the cloud's grid in row-major order, one thread per pixel: the pixel's 29
+//              terms in fp64 (the upper triangle of J J^T, J e, e e and 1; 29 times +0 for a pixel without a pair), summed over the wave by a
+//              butterfly and over the four waves in wave order (common.hpp's block_sum_store), one row of 29 doubles per tile in the workspace
+//   icp_total  one workgroup: thread j adds value j of the tiles in index order, starting from tile 0's, and stores sums[j]
+// The two cameras travel in the launch arguments, read from host memory before the call returns: the live pose changes with every iteration and
+// nothing is staged.  The model is addressed only after its pixel passed the range test in fp64, and the live frame only inside the grid, so a
+// guess that looks anywhere reads nothing outside the arrays.
+// No atomics, no workgroup waits for another, a fixed order of every addition: the same input gives the same bits on every call.  Every slot of
+// the workspace that is read and all 29 outputs are written on every call.  Contraction is off for the whole file and the division is IEEE's.
+#include <cmath>
+
+#include "ops.hpp"
+
+#include "cloud_common.hpp"  // depth_value, kept, source_pixel, check_selection: shared with pointcloud.hip and tsdf.hip
+
+namespace edv {
+namespace {
+
+constexpr int ICP_THREADS = 256;
+constexpr int ICP_TILE = ICP_THREADS;  // output pixels per workgroup: the one constant behind icp_tile_pixels()
+constexpr int ICP_TERMS = 29;
+constexpr int ICP_TOTAL_THREADS = 64;
+
+struct IcpCams {
+    double live[21];   // Kinv[3][3], R[3][3], t[3] of the estimate
+    double model[39];  // the model view's Kinv, R, t, then W[3][4] and K00 K01 K02 K10 K11 K12
+};
+
+// (M[0]*a + M[1]*b) + M[2]*c for the three rows of a row-major 3 x 3
+__device__ __forceinline__ void rows3(const double *M, double a, double b, double c, double (&o)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = (M[3 * i] * a + M[3 * i + 1] * b) + M[3 * i + 2] * c;
+}
+
+// the 29 terms of output pixel q < grid_pixels of the live frame; false, with `a` untouched, for a pixel without a pair
+__device__ __forceinline__ bool icp_terms(const CloudSel &s, const IcpCams &c, const float *__restrict__ xf, const uint8_t *__restrict__ mf, int ow, unsigned q,
+                                          const float *__restrict__ model_depth, const float *__restrict__ model_normals, int mh, int mw, double max_dist2,
+                                          double (&a)[ICP_TERMS]) {
+    int ox, oy;
+    const int p = source_pixel(s, ow, q, ox, oy);
+    float z;
+    if (!kept(s, xf[p], mf ? mf[p] : 1u, z)) return false;
+    const double u = ((double)ox + 0.5) * (double)s.step, v = ((double)oy + 0.5) * (double)s.step;
+    double l[3], r[3], rho[3], P[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) l[i] = (c.live[3 * i] * u + c.live[3 * i + 1] * v) + c.live[3 * i + 2];
+    rows3(c.live + 9, l[0], l[1], l[2], r);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) rho[i] = r[i] * (double)z, P[i] = c.live[18 + i] + rho[i];
+    // into the model view, as tsdf_integrate projects a voxel centre
+    const double *W = c.model + 21, *K = c.model + 33;
+    const double q2 = ((W[8] * P[0] + W[9] * P[1]) + W[10] * P[2]) + W[11];
+    if (!(q2 > 0.0)) return false;  // behind the model camera, or NaN
+    const double q0 = ((W[0] * P[0] + W[1] * P[1]) + W[2] * P[2]) + W[3];
+    const double q1 = ((W[4] * P[0] + W[5] * P[1]) + W[6] * P[2]) + W[7];
+    const double um = ((K[0] * q0 + K[1] * q1) + K[2] * q2) / q2;
+    const double vm = ((K[3] * q0 + K[4] * q1) + K[5] * q2) / q2;
+    if (!(um >= 0.0 && um < (double)mw && vm >= 0.0 && vm < (double)mh)) return false;  // in fp64, before any conversion: 0 <= px < mw and 0 <= py < mh below
+    const int px = (int)um, py = (int)vm;
+    const size_t at = (size_t)py * (unsigned)mw + (unsigned)px;
+    const float dm = model_depth[at];
+    if (!(dm > 0.0f)) return false;  // a miss is +0; NaN fails
+    const double N[3] = {(double)model_normals[at * 3], (double)model_normals[at * 3 + 1], (double)model_normals[at * 3 + 2]};
+    if (!((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2] > 0.0)) return false;
+    // the model's vertex: the cloud's lift of its own pixel centre
+    const double mu = (double)px + 0.5, mv = (double)py + 0.5;
+    double lm[3], rm[3], D[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) lm[i] = (c.model[3 * i] * mu + c.model[3 * i + 1] * mv) + c.model[3 * i + 2];
+    rows3(c.model + 9, lm[0], lm[1], lm[2], rm);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) D[i] = (c.model[18 + i] + rm[i] * (double)dm) - P[i];
+    if (!((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2] <= max_dist2)) return false;
+    const double e = (N[0] * D[0] + N[1] * D[1]) + N[2] * D[2];
+    const double J[6] = {rho[1] * N[2] - rho[2] * N[1], rho[2] * N[0] - rho[0] * N[2], rho[0] * N[1] - rho[1] * N[0], N[0], N[1], N[2]};
+    int t = 0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+#pragma unroll
+        for (int k = j; k < 6; ++k) a[t++] = J[j] * J[k];
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a[21 + j] = J[j] * e;
+    a[27] = e * e;
+    a[28] = 1.0;
+    return true;
+}
+
+// grid: tiles.  tile_sums [tiles][29]
+__global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(CloudSel s, long long frame, IcpCams c, int ow, unsigned grid_pixels, const float *__restrict__ model_depth,
+                                                               const float *__restrict__ model_normals, int mh, int mw, double max_dist2,
+                                                               double *__restrict__ tile_sums) {
+    const unsigned q = blockIdx.x * (unsigned)ICP_TILE + threadIdx.x;
+    double a[ICP_TERMS];
+    bool pair = false;
+    if (q < grid_pixels) {
+        const float *xf = s.x + frame * s.h * s.w;
+        const uint8_t *mf = s.mask ? s.mask + frame * s.mask_stride : nullptr;
+        pair = icp_terms(s, c, xf, mf, ow, q, model_depth, model_normals, mh, mw, max_dist2, a);
+    }
+    if (!pair) {
+#pragma unroll
+        for (int j = 0; j < ICP_TERMS; ++j) a[j] = 0.0;
+    }
+    // every thread of the workgroup: a butterfly over each wave, then ((w0 + w1) + w2) + w3
+    block_sum_store<ICP_TERMS>(a, tile_sums + (size_t)blockIdx.x * ICP_TERMS);
+}
+
+// one workgroup: sums[j] = (((t_0 + t_1) + t_2) + ...)[j], tile by tile.  The loads of eight tiles are issued together; the additions keep their order.
+__global__ __launch_bounds__(ICP_TOTAL_THREADS) void icp_total_kernel(const double *__restrict__ tile_sums, unsigned tiles, double *__restrict__ sums) {
+    const unsigned j = threadIdx.x;
+    if (j >= (unsigned)ICP_TERMS) return;
+    double t = tile_sums[j];
+    unsigned i = 1;
+    for (; i + 8 <= tiles; i += 8) {
+        double v[8];
+#pragma unroll
+        for (unsigned k = 0; k < 8; ++k) v[k] = tile_sums[(size_t)(i + k) * ICP_TERMS + j];
+#pragma unroll
+        for (unsigned k = 0; k < 8; ++k) t = t + v[k];
+    }
+    for (; i < tiles; ++i) t = t + tile_sums[(size_t)i * ICP_TERMS + j];
+    sums[j] = t;
+}
+
+inline bool icp_shape_ok(int h, int w, int step) { return h >= 1 && w >= 1 && step >= 1 && (long long)h * w < (1ll << 31); }
+
+struct IcpGrid {
+    int ow;
+    unsigned pixels;  // oh * ow <= h * w < 2^31
+    unsigned tiles;
+};
+
+inline IcpGrid icp_grid(int h, int w, int step) {
+    const long long oh = ((long long)h + step - 1) / step, ow = ((long long)w + step - 1) / step;
+    return {(int)ow, (unsigned)(oh * ow), (unsigned)((oh * ow + ICP_TILE - 1) / ICP_TILE)};
+}
+
+}  // namespace
+
+int icp_tile_pixels() { return ICP_TILE; }
+
+size_t icp_workspace(int h, int w, int step) {
+    if (!icp_shape_ok(h, w, step)) return 0;
+    return (size_t)icp_grid(h, w, step).tiles * ICP_TERMS * sizeof(double);
+}
+
+int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
+             double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
+    EDV_TRY(check_selection(s));
+    EDV_CHECK(frame >= 0 && frame < s.n, "frame outside the clip");
+    EDV_CHECK(live_cam && model_cam, "null cameras");
+    EDV_CHECK(model_depth && model_normals && aligned_to(model_depth, 4) && aligned_to(model_normals, 4), "model depth or normals missing or not 4-byte aligned");
+    EDV_CHECK(mh >= 1 && mw >= 1 && (long long)mh * mw < (1ll << 31), "mh and mw must be at least 1 and the model view below 2^31 pixels");
+    EDV_CHECK(std::isfinite(max_dist2) && max_dist2 >= 0.0, "max_dist2 must be finite and >= 0");
+    EDV_CHECK(sums && aligned_to(sums, 8), "sums missing or not 8-byte aligned");
+    EDV_CHECK(ws && aligned_to(ws, 8) && ws_bytes >= icp_workspace(s.h, s.w, s.step), "workspace missing, too small or not 8-byte aligned (edv_icp_workspace)");
+    const IcpGrid g = icp_grid(s.h, s.w, s.step);
+    IcpCams c;
+    for (int i = 0; i < 21; ++i) c.live[i] = live_cam[i];
+    for (int i = 0; i < 39; ++i) c.model[i] = model_cam[i];
+    double *tile_sums = static_cast<double *>(ws);
+    EDV_LAUNCH(icp_tile_kernel, dim3(g.tiles), dim3(ICP_THREADS), 0, stream, s, frame, c, g.ow, g.pixels, model_depth, model_normals, mh, mw, max_dist2, tile_sums);
+    EDV_LAUNCH_OK();
+    EDV_LAUNCH(icp_total_kernel, dim3(1), dim3(ICP_TOTAL_THREADS), 0, stream, tile_sums, g.tiles, sums);
+    EDV_LAUNCH_OK();
+    return 0;
+}
+
+}  // namespace edv

@@ -846,7 +846,7 @@ class endodav(nn.Module):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             return cloud.lift(depth, spec, frames=rgb, output=output)
 
-    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host", surface="points", views=None):
+    def video_surface(self, frames, spec, volume, input_size=518, device="cuda", min_weight=1.0, output="host", surface="points", views=None, track=None):
         """A video as one coloured surface (not in the reference): ``infer_video_depth(frames, stitch="device", output="device")``, then every
         frame integrated into the TSDF ``volume`` (a ``fusion.Volume``) with ``spec`` (a ``cloud.Cloud`` with ``step=1``: intrinsics, poses,
         depth rule and mask) and the uint8 frames, uploaded once, as the colours, then the zero crossings of the volume between voxels of
@@ -854,7 +854,10 @@ class endodav(nn.Module):
         Returns a ``cloud.PointCloud`` with ``offsets = [0, total]``: numpy arrays, or with ``output="device"`` tensors on the GPU.
         ``surface="mesh"`` returns the triangle mesh of the volume instead, a ``fusion.Mesh`` with normals and colours (``fusion.Tsdf.mesh``).
         ``surface="views"`` returns the volume as the cameras ``views`` (a ``fusion.Views``) see it, a ``fusion.Raycast`` of depth, normal and
-        colour maps (``fusion.Tsdf.raycast``)."""
+        colour maps (``fusion.Tsdf.raycast``).
+        ``track`` (a ``fusion.Track``): the video comes without poses.  ``spec`` then holds exactly one pose, the first camera's; every later
+        frame is tracked against the volume from the previous frame's pose and integrated where it was found (``fusion.Tsdf.track_clip``), and
+        the call returns (the surface, a ``fusion.Tracked`` with the poses found), for every ``surface``."""
         from . import cloud, fusion
 
         if surface not in ("points", "mesh", "views"):
@@ -871,17 +874,29 @@ class endodav(nn.Module):
         if surface == "views":
             fusion._check_raycast(views, min_weight, True, output)
             views.march(volume.voxel)
+        if track is not None:
+            if not isinstance(track, fusion.Track):
+                raise ValueError(f"track must be a fusion.Track, got {type(track).__name__}")
+            if spec.pose.shape[0] != 1:
+                raise ValueError(f"tracking starts from exactly one pose, the first camera's; the Cloud holds {spec.pose.shape[0]}")
+            track.views(spec.K[0], spec.pose[0], (1, 1)).march(volume.voxel)
         frames = np.ascontiguousarray(frames)
         depth = self.infer_video_depth(frames, input_size=input_size, device=device, stitch="device", output="device")
         with torch.cuda.device(depth.device):
             rgb = torch.from_numpy(frames if frames.flags.writeable else frames.copy()).to(depth.device)
             tsdf = fusion.Tsdf(volume, coloured=True, device=depth.device)
-            tsdf.integrate(depth, spec, frames=rgb)
+            tracked = None
+            if track is None:
+                tsdf.integrate(depth, spec, frames=rgb)
+            else:
+                tracked = tsdf.track_clip(depth, spec, track, frames=rgb)
             if surface == "views":
-                return tsdf.raycast(views, min_weight=min_weight, output=output)
-            if surface == "mesh":
-                return tsdf.mesh(min_weight=min_weight, output=output)
-            return tsdf.surface(min_weight=min_weight, output=output)
+                found = tsdf.raycast(views, min_weight=min_weight, output=output)
+            elif surface == "mesh":
+                found = tsdf.mesh(min_weight=min_weight, output=output)
+            else:
+                found = tsdf.surface(min_weight=min_weight, output=output)
+            return found if track is None else (found, tracked)
 
     def stream_video_depth(self, frame_shape, device="cuda", output="host", render=None):
         """``infer_video_depth(stitch="device")`` for a live feed (not in the reference): returns a ``video.DepthStream`` whose

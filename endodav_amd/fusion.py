@@ -1,5 +1,5 @@
 """Surface fusion on the GPU (opt-in): a depth video with its poses integrated into one truncated signed distance (TSDF) volume, and the zero
-crossings of that volume as one coloured point list, as one coloured, oriented, indexed triangle mesh, or as depth, normal and colour maps seen from given cameras.  Not in the reference, whose ``3d_reconstruction`` clouds concatenate every frame's points:
+crossings of that volume as one coloured point list, as one coloured, oriented, indexed triangle mesh, or as depth, normal and colour maps seen from given cameras; and the camera tracked against that volume where the video comes without poses.  Not in the reference, whose ``3d_reconstruction`` clouds concatenate every frame's points:
 a thousand re-observations of the same tissue, each frame's depth noise a shell of its own.  Here every voxel averages what the frames saw.
 
 ``Volume`` says where the voxels are; ``Tsdf`` owns the arrays on the GPU (``edv_tsdf_integrate`` / ``edv_tsdf_count`` / ``edv_tsdf_extract``,
@@ -82,10 +82,41 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
                       volume with some n_i = 1 has no cell: every pixel is a miss.
             The depth is the cloud's: ``cloud.lift(depth, Cloud(K, pose, source="depth"))`` puts the hits back in the world.
 
-What is not built: hashed or sparse volumes, shading, free-space skipping, and pose estimation; poses are inputs, as for the cloud."""
+  tracking  the pose of a frame found against the volume (``Track``, ``Tsdf.track`` / ``TsdfHost.track``, ``track_clip`` -> ``Tracked``;
+            ``edv_icp_sums``): frame-to-model point-to-plane ICP with projective association.  The volume is ray-cast once from the guess (one
+            view with normals: the model); then ``iterations`` times the normal equations are summed on the GPU (``icp_sums``; ``icp_sums_host``
+            is the mirror), solved on the host (``icp_solve``) and the twist applied (``apply_twist``).  Solve and twist are plain float64 numpy
+            and the same functions for both classes, so a whole track differs only in where the sums came from.
+            pixel     output pixel (oy, ox) of the cloud's grid of the live frame; z (float32) and kept are the cloud's.  float64, every
+                      operation rounded on its own, with Kinv, R, t of the current estimate:
+                      u = (ox + 0.5) * step, v = (oy + 0.5) * step;  l_i = (Kinv[i,0]*u + Kinv[i,1]*v) + Kinv[i,2];
+                      r_i = (R[i,0]*l_0 + R[i,1]*l_1) + R[i,2]*l_2;  rho_i = r_i * float64(z);  P_i = t_i + rho_i
+            project   into the model's view exactly as integrate projects a voxel centre (W, K of ``cameras``):
+                      q_i = ((W[i,0]*P_x + W[i,1]*P_y) + W[i,2]*P_z) + W[i,3];  skip unless q_2 > 0;
+                      um = ((K00*q_0 + K01*q_1) + K02*q_2) / q_2, vm likewise;  skip unless 0 <= um < mw and 0 <= vm < mh;  px = int(um), py = int(vm)
+            model     dm = depth[py, px], skip unless dm > 0 (a miss is 0);  N = float64(normals[py, px]), skip unless (N_x*N_x + N_y*N_y) + N_z*N_z > 0;
+                      the vertex is the cloud's lift of the model's own pixel centre (px + 0.5, py + 0.5) at depth dm through the model's
+                      Kinv, R, t:  V_i = t_m,i + rm_i * float64(dm);  D_i = V_i - P_i;  skip unless (D_x*D_x + D_y*D_y) + D_z*D_z <= max_dist^2
+            terms     e = (N_x*D_x + N_y*D_y) + N_z*D_z;  c = rho x N (each product rounded, then the difference);  J = (c, N): the twist is
+                      about the live camera centre, which keeps the system well conditioned far from the world origin.  29 terms a pixel:
+                      J_j*J_k for j <= k, row-major (21), J_j*e (6), e*e, 1.  A pixel without a pair contributes 29 times +0.
+            sums      float64, no atomics, a fixed order: tiles of 256 output pixels in row-major order, a wave 64 of them; inside a wave a
+                      butterfly (s = 32, 16, 8, 4, 2, 1: x <- x + x[lane ^ s]), the tile ((w0 + w1) + w2) + w3, then the tiles in index order
+                      starting from tile 0's value.  sums[28] is the number of pairs, sqrt(sums[27] / sums[28]) their rms distance to the planes.
+            solve     the symmetric 6 x 6 system by ``np.linalg.solve``; lost when there are fewer than ``min_pairs`` pairs, the solve raises or
+                      the solution is not finite.  A lost frame returns its guess.
+            twist     xi = (rotation vector, translation):  R <- Rodrigues(xi[:3]) @ R, t <- t + xi[3:].  After the last step R is replaced by
+                      U @ Vt of its SVD.
+            clip      ``track_clip``: the Cloud holds one pose, the first camera's.  Frame 0 is integrated there; each later frame is tracked from
+                      the previous frame's pose and integrated at the pose found; a lost frame keeps the previous pose and is not integrated.
+            A scene that is a plane leaves sliding inside the plane unobservable; that is not detected.
+
+What is not built: hashed or sparse volumes, shading, free-space skipping, and in the tracker image pyramids, compatibility tests between live and
+model normals, robust weights, loop closure and relocalisation after a lost frame."""
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import itertools
 import math
 from dataclasses import KW_ONLY, dataclass
@@ -345,6 +376,312 @@ def _staged(a: np.ndarray, dev: torch.device) -> torch.Tensor:
     return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
 
 
+# ---- tracking -------------------------------------------------------------------------------------------------------------------------------
+ICP_TERMS = 29   # the upper triangle of J J^T (21), J e (6), e e, and the count
+ICP_TILE = 256   # output pixels per tile of the ordered sum: edv_icp_tile_pixels()
+_LANE = np.arange(64)
+
+
+def _number(x) -> bool:
+    return isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool) and math.isfinite(x)
+
+
+@dataclass(frozen=True, eq=False)
+class Track:
+    """How a frame is tracked against the volume (module docstring, "tracking")."""
+    _: KW_ONLY
+    near: float                              # the range of the model's ray-cast, as in ``Views``
+    far: float
+    step: float = None                       # depth between two samples of the ray-cast; None = the volume's voxel
+    iterations: int = 6                      # ICP steps per frame
+    max_dist: float = None                   # pairs farther apart than this are dropped; None = the volume's trunc
+    min_pairs: int = 64                      # fewer pairs than this: the frame is lost
+    min_weight: float = 1.0                  # of the ray-cast
+
+    def __post_init__(self):
+        for name in ("near", "far"):
+            if not _number(getattr(self, name)):
+                raise ValueError(f"{name} must be a finite number, got {getattr(self, name)!r}")
+            object.__setattr__(self, name, float(getattr(self, name)))
+        if not 0.0 <= self.near < self.far:
+            raise ValueError(f"need 0 <= near < far, got near={self.near!r}, far={self.far!r}")
+        for name in ("step", "max_dist"):
+            x = getattr(self, name)
+            if x is not None:
+                if not _positive(x):
+                    raise ValueError(f"{name} must be finite and positive, got {x!r}")
+                object.__setattr__(self, name, float(x))
+        for name in ("iterations", "min_pairs"):
+            x = getattr(self, name)
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {x!r}")
+            object.__setattr__(self, name, int(x))
+        _check_surface(self.min_weight, "host")
+        object.__setattr__(self, "min_weight", float(self.min_weight))
+
+    def views(self, K, pose, size) -> Views:
+        """The one view the model is cast from."""
+        return Views(K, pose, size=size, near=self.near, far=self.far, step=self.step)
+
+
+@dataclass(eq=False)
+class Tracked:
+    """What ``track_clip`` found, per frame; numpy arrays on the host."""
+    poses: np.ndarray                        # float64 [n, 4, 4] T_world_camera; a lost frame repeats the previous pose
+    pairs: np.ndarray                        # int64 [n], the pairs of the last ICP step; 0 for frame 0
+    rms: np.ndarray                          # float64 [n], the root mean square point-to-plane distance of those pairs; 0 for frame 0
+    lost: np.ndarray                         # bool [n]; a lost frame is not integrated
+
+
+def _check_icp(depth, spec, model, views, max_dist, frame):
+    """(n, h, w, mask, cams [1 or n, 21], the model's 39 doubles) of checked arguments."""
+    n, h, w = _check_clip(depth, spec, None)
+    if not 1 <= n <= MAX_FRAMES or h < 1 or w < 1:
+        raise ValueError(f"1 to {MAX_FRAMES} frames that are not empty, got {n} x {h} x {w}")
+    if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
+        raise ValueError(f"frame must be an integer in 0 .. {n - 1}, got {frame!r}")
+    if not isinstance(views, Views) or views.count != 1:
+        raise ValueError("views must be a fusion.Views of one view, the one the model was cast from")
+    if not isinstance(model, Raycast) or model.normals is None:
+        raise ValueError("model must be a fusion.Raycast with normals")
+    mh, mw = views.size
+    for a, shape, what in ((model.depth, (1, mh, mw), "depth"), (model.normals, (1, mh, mw, 3), "normals")):
+        if tuple(a.shape) != shape or str(a.dtype).replace("torch.", "") != "float32":
+            raise ValueError(f"expected the model's {what} as float32 {list(shape)}, got {a.dtype} {tuple(a.shape)}")
+    if not _number(max_dist) or max_dist < 0.0:
+        raise ValueError(f"max_dist must be finite and >= 0, got {max_dist!r}")
+    model_cam = np.concatenate([views.cams()[0], cameras(Cloud(K=views.K, pose=views.pose), 1)[0]])
+    return n, h, w, spec.frame_mask(n, h, w), spec.cams(n), model_cam
+
+
+def _pose4(pose34) -> np.ndarray:
+    T = np.eye(4)
+    T[:3, :] = pose34
+    return T
+
+
+def _live_cam(kinv9, T) -> np.ndarray:
+    """The row of ``Cloud.cams`` of the pose T with the inverse intrinsics kinv9."""
+    return np.concatenate([kinv9, T[:3, :3].reshape(9), T[:3, 3]])
+
+
+def _ordered_sum(terms: np.ndarray) -> np.ndarray:
+    """float64 [p, 29] per output pixel in row-major order -> [29], added in the kernel's order: tiles of 256 pixels, a wave 64 of them; a
+    butterfly inside the wave, the four waves in order, then the tiles in order, starting from tile 0's value."""
+    p = terms.shape[0]
+    tiles = -(-p // ICP_TILE)
+    x = np.zeros((tiles * ICP_TILE, ICP_TERMS))
+    x[:p] = terms
+    x = x.reshape(tiles, ICP_TILE // 64, 64, ICP_TERMS)
+    for s in (32, 16, 8, 4, 2, 1):
+        x = x + x[:, :, _LANE ^ s, :]
+    wave = x[:, :, 0, :]
+    tile = ((wave[:, 0] + wave[:, 1]) + wave[:, 2]) + wave[:, 3]
+    total = tile[0].copy()
+    for b in range(1, tiles):
+        total = total + tile[b]
+    return total
+
+
+class _IcpHost:
+    """One live frame against one model view in numpy: what does not depend on the estimate is formed once."""
+    output = "host"
+
+    def __init__(self, depth, spec, model, views, max_dist, frame):
+        depth = np.asarray(depth)
+        n, h, w, mask, cams, self.model_cam = _check_icp(depth, spec, model, views, max_dist, frame)
+        self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
+        self.max_dist2 = float(max_dist) * float(max_dist)
+        step = int(spec.step)
+        oh, ow = -(-h // step), -(-w // step)
+        sy = np.minimum(np.arange(oh, dtype=np.int64) * step + step // 2, h - 1)
+        sx = np.minimum(np.arange(ow, dtype=np.int64) * step + step // 2, w - 1)
+        lo, span, gain, near, far = spec.scalars()
+        x = depth[frame][sy][:, sx]
+        with np.errstate(all="ignore"):
+            if spec.source == "depth":
+                z = x * gain
+            else:
+                scaled = lo + span * x
+                z = np.float32(1.0) / scaled
+                z = z * gain
+            keep = (z > near) & (z < far)
+        if mask is not None:
+            keep &= (mask[frame] if mask.ndim == 3 else mask)[sy][:, sx] != 0
+        self.z, self.keep = z.astype(np.float64).reshape(-1), keep.reshape(-1)
+        self.u = np.broadcast_to(((np.arange(ow, dtype=np.float64) + 0.5) * float(step))[None, :], (oh, ow)).reshape(-1)
+        self.v = np.broadcast_to(((np.arange(oh, dtype=np.float64) + 0.5) * float(step))[:, None], (oh, ow)).reshape(-1)
+        self.depth, self.normals = np.asarray(model.depth)[0], np.asarray(model.normals)[0]
+
+    def terms(self, live: np.ndarray) -> np.ndarray:
+        """float64 [oh * ow, 29]: the terms of every output pixel for the estimate ``live`` (21 doubles), +0 where there is no pair."""
+        kinv, rot, pos = live[:9].reshape(3, 3), live[9:18].reshape(3, 3), live[18:]
+        m = self.model_cam
+        kinv_m, rot_m, pos_m, W, K = m[:9].reshape(3, 3), m[9:18].reshape(3, 3), m[18:21], m[21:33].reshape(3, 4), m[33:].reshape(2, 3)
+        mh, mw = self.depth.shape
+        u, v, z = self.u, self.v, self.z
+        with np.errstate(all="ignore"):
+            l = [(kinv[i, 0] * u + kinv[i, 1] * v) + kinv[i, 2] for i in range(3)]
+            r = [(rot[i, 0] * l[0] + rot[i, 1] * l[1]) + rot[i, 2] * l[2] for i in range(3)]
+            rho = [r[i] * z for i in range(3)]
+            P = [pos[i] + rho[i] for i in range(3)]
+            q = [((W[i, 0] * P[0] + W[i, 1] * P[1]) + W[i, 2] * P[2]) + W[i, 3] for i in range(3)]
+            ok = self.keep & (q[2] > 0.0)
+            um = ((K[0, 0] * q[0] + K[0, 1] * q[1]) + K[0, 2] * q[2]) / q[2]
+            vm = ((K[1, 0] * q[0] + K[1, 1] * q[1]) + K[1, 2] * q[2]) / q[2]
+            ok &= (um >= 0.0) & (um < float(mw)) & (vm >= 0.0) & (vm < float(mh))
+            px, py = np.where(ok, um, 0.0).astype(np.int64), np.where(ok, vm, 0.0).astype(np.int64)
+            dm = self.depth[py, px]
+            ok &= dm > 0
+            N = [self.normals[py, px, i].astype(np.float64) for i in range(3)]
+            ok &= (N[0] * N[0] + N[1] * N[1]) + N[2] * N[2] > 0.0
+            mu, mv = px.astype(np.float64) + 0.5, py.astype(np.float64) + 0.5
+            lm = [(kinv_m[i, 0] * mu + kinv_m[i, 1] * mv) + kinv_m[i, 2] for i in range(3)]
+            rm = [(rot_m[i, 0] * lm[0] + rot_m[i, 1] * lm[1]) + rot_m[i, 2] * lm[2] for i in range(3)]
+            D = [(pos_m[i] + rm[i] * dm.astype(np.float64)) - P[i] for i in range(3)]
+            ok &= (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2] <= self.max_dist2
+            e = (N[0] * D[0] + N[1] * D[1]) + N[2] * D[2]
+            J = [rho[1] * N[2] - rho[2] * N[1], rho[2] * N[0] - rho[0] * N[2], rho[0] * N[1] - rho[1] * N[0], N[0], N[1], N[2]]
+            cols = [J[j] * J[k] for j in range(6) for k in range(j, 6)] + [J[j] * e for j in range(6)] + [e * e, np.ones_like(e)]
+            return np.stack([np.where(ok, c, 0.0) for c in cols], axis=1)
+
+    def sums(self, live: np.ndarray) -> np.ndarray:
+        return _ordered_sum(self.terms(live))
+
+
+class _IcpDevice:
+    """The same on the GPU (``edv_icp_sums``): the clip, the mask, the model and the workspace are placed once, an estimate costs two launches
+    and one 232-byte read, for which the host waits."""
+    output = "device"
+
+    def __init__(self, depth, spec, model, views, max_dist, frame, device=None):
+        if isinstance(depth, torch.Tensor):
+            if not depth.is_cuda:
+                raise ValueError("a depth tensor must live on the GPU (pass host data as a numpy array)")
+            device = depth.device
+        else:
+            depth = np.asarray(depth)
+        n, h, w, mask, cams, model_cam = _check_icp(depth, spec, model, views, max_dist, frame)
+        if device is None:
+            device = model.depth.device if isinstance(model.depth, torch.Tensor) and model.depth.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        self.device, self.frame, self.lib = device, int(frame), _lib.load()
+        self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
+        self.max_dist2 = float(max_dist) * float(max_dist)
+        self.model_cam = (C.c_double * 39)(*model_cam)
+        self.size = views.size
+        with torch.cuda.device(device):
+            self.x = _on_device(depth, device)
+            self.mask = None if mask is None else _staged(mask, device)
+            self.sel = selection(self.x, spec, self.mask)
+            self.depth, self.normals = _on_device(model.depth, device), _on_device(model.normals, device)
+            self.ws = torch.empty(max(int(self.lib.edv_icp_workspace(h, w, int(spec.step))), 8), dtype=torch.uint8, device=device)
+            self.sums_d = torch.empty(ICP_TERMS, dtype=torch.float64, device=device)
+            self.sums_h = torch.empty(ICP_TERMS, dtype=torch.float64, pin_memory=True)
+
+    def sums(self, live: np.ndarray) -> np.ndarray:
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            _lib.check(self.lib.edv_icp_sums(C.byref(self.sel), self.frame, (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(), self.normals.data_ptr(),
+                                             self.size[0], self.size[1], self.max_dist2, self.sums_d.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                             C.c_void_p(stream.cuda_stream)), "edv_icp_sums")
+            self.sums_h.copy_(self.sums_d, non_blocking=True)
+            stream.synchronize()
+            return self.sums_h.numpy().copy()
+
+
+def _estimate(ctx, spec: Cloud, frame: int) -> np.ndarray:
+    return _live_cam(ctx.kinv, _pose4(spec.pose[frame if spec.pose.shape[0] > 1 else 0]))
+
+
+def icp_sums(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0) -> np.ndarray:
+    """float64 [29]: the sums of one point-to-plane step (module docstring, "tracking") between frame ``frame`` of ``depth`` (float32 [n, h, w], a
+    numpy array or a tensor on the GPU, as for ``Tsdf.integrate``), lifted through ``spec`` whose pose is the estimate, and ``model``, a one-view
+    ``Raycast`` with normals (arrays or tensors) cast from ``views``.  On the GPU, on the caller's current stream; the host waits for the result."""
+    ctx = _IcpDevice(depth, spec, model, views, max_dist, frame)
+    return ctx.sums(_estimate(ctx, spec, frame))
+
+
+def icp_sums_host(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0) -> np.ndarray:
+    """``icp_sums`` in numpy, the same operations in the same order: the two agree bit for bit."""
+    ctx = _IcpHost(depth, spec, model, views, max_dist, frame)
+    return ctx.sums(_estimate(ctx, spec, frame))
+
+
+def icp_solve(sums, min_pairs):
+    """The twist xi [6] (rotation vector, then translation) of the normal equations in ``sums``, or None when the frame is lost: fewer than
+    ``min_pairs`` pairs, a singular system, or a solution that is not finite."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if not sums[28] >= min_pairs:
+        return None
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = sums[:21]
+    A = A + np.triu(A, 1).T
+    try:
+        xi = np.linalg.solve(A, sums[21:27])
+    except np.linalg.LinAlgError:
+        return None
+    return xi if np.isfinite(xi).all() else None
+
+
+def apply_twist(T, xi) -> np.ndarray:
+    """T_world_camera [4, 4] moved by xi: R <- Rodrigues(xi[:3]) @ R about the camera centre, t <- t + xi[3:]."""
+    T, xi = np.array(T, dtype=np.float64), np.asarray(xi, dtype=np.float64)
+    theta = math.sqrt(float(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]))
+    if theta > 0.0:
+        a = xi[:3] / theta
+        A = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        T[:3, :3] = (np.eye(3) + math.sin(theta) * A + (1.0 - math.cos(theta)) * (A @ A)) @ T[:3, :3]
+    T[:3, 3] = T[:3, 3] + xi[3:]
+    return T
+
+
+def _track(tsdf, context, depth, spec, track, frame):
+    """``Tsdf.track`` and ``TsdfHost.track``: everything but the sums is this host code."""
+    if not isinstance(track, Track):
+        raise ValueError(f"track must be a fusion.Track, got {type(track).__name__}")
+    n, h, w = _check_clip(depth, spec, None)
+    if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
+        raise ValueError(f"frame must be an integer in 0 .. {n - 1}, got {frame!r}")
+    guess = _pose4(spec.pose[frame if spec.pose.shape[0] > 1 else 0])
+    views = track.views(spec.K[frame if spec.K.shape[0] > 1 else 0], guess, (h, w))
+    model = tsdf.raycast(views, min_weight=track.min_weight, normals=True, output=context.output)
+    ctx = context(depth, spec, model, views, tsdf.volume.trunc if track.max_dist is None else track.max_dist, frame)
+    T, pairs, rms = guess.copy(), 0, float("nan")
+    for _ in range(track.iterations):
+        sums = ctx.sums(_live_cam(ctx.kinv, T))
+        pairs = int(sums[28])
+        rms = math.sqrt(sums[27] / sums[28]) if sums[28] > 0.0 else float("nan")
+        xi = icp_solve(sums, track.min_pairs)
+        if xi is None:
+            return guess, pairs, rms, True
+        T = apply_twist(T, xi)
+    U, _, Vt = np.linalg.svd(T[:3, :3])
+    T[:3, :3] = U @ Vt
+    return T, pairs, rms, False
+
+
+def _track_clip(tsdf, depth, spec, track, frames):
+    """``Tsdf.track_clip`` and ``TsdfHost.track_clip``."""
+    if not isinstance(track, Track):
+        raise ValueError(f"track must be a fusion.Track, got {type(track).__name__}")
+    n, h, w, _, mask = _check_integrate(depth, spec, frames, tsdf.coloured)
+    if spec.pose.shape[0] != 1:
+        raise ValueError(f"tracking starts from one pose, the first camera's; the Cloud holds {spec.pose.shape[0]}")
+    out = Tracked(np.zeros((n, 4, 4)), np.zeros(n, np.int64), np.zeros(n), np.zeros(n, bool))
+    T = _pose4(spec.pose[0])
+    for i in range(n):
+        one = dataclasses.replace(spec, K=spec.K[i if spec.K.shape[0] > 1 else 0], pose=T, mask=mask[i] if mask is not None and mask.ndim == 3 else mask)
+        if i:
+            found, out.pairs[i], out.rms[i], out.lost[i] = tsdf.track(depth[i:i + 1], one, track)
+            if not out.lost[i]:
+                T = found
+                one = dataclasses.replace(one, pose=T)
+        out.poses[i] = T
+        if not out.lost[i]:
+            tsdf.integrate(depth[i:i + 1], one, None if frames is None else frames[i:i + 1])
+    return out
+
+
 class TsdfHost:
     """The numpy mirror of the kernels (module docstring): vectorised over the voxels, a loop over the frames."""
 
@@ -579,6 +916,14 @@ class TsdfHost:
                     colors[f, rays] = np.minimum(np.float32(255.0), np.maximum(np.float32(0.0), np.floor(col + np.float32(0.5)))).astype(np.uint8)
         return shaped
 
+    def track(self, depth, spec: Cloud, track: Track, frame: int = 0):
+        """The mirror of ``Tsdf.track``: the same host code around ``icp_sums_host``."""
+        return _track(self, _IcpHost, np.asarray(depth), spec, track, frame)
+
+    def track_clip(self, depth, spec: Cloud, track: Track, frames=None) -> Tracked:
+        """The mirror of ``Tsdf.track_clip``."""
+        return _track_clip(self, np.asarray(depth), spec, track, None if frames is None else np.asarray(frames))
+
 
 class Tsdf:
     """A TSDF volume on the GPU.  ``integrate`` folds clips into it, ``surface`` and ``mesh`` read its zero crossings, ``raycast`` views it from
@@ -734,6 +1079,27 @@ class Tsdf:
                     hst.copy_(o, non_blocking=True)
             stream.synchronize()
             return Raycast(*(None if hst is None else hst.numpy() for hst in host))
+
+    def _own(self, depth):
+        if isinstance(depth, torch.Tensor) and (not depth.is_cuda or depth.device != self.device):
+            raise ValueError(f"a depth tensor must live on the volume's GPU {self.device} (pass host data as a numpy array)")
+        return depth if isinstance(depth, torch.Tensor) else np.asarray(depth)
+
+    def track(self, depth, spec: Cloud, track: Track, frame: int = 0):
+        """The pose of frame ``frame`` of ``depth`` (as for ``integrate``) against this volume (module docstring, "tracking"): the volume ray-cast
+        once from the guess, which is ``spec.pose`` with ``spec.K`` and the frame's size, then ``track.iterations`` steps of sums on the GPU, a
+        6 x 6 solve on the host and the twist applied.  Returns (T_world_camera float64 [4, 4], pairs, rms, lost); a lost frame returns the
+        guess.  On the caller's current stream; the host waits once per step."""
+        with torch.cuda.device(self.device):
+            return _track(self, _IcpDevice, self._own(depth), spec, track, frame)
+
+    def track_clip(self, depth, spec: Cloud, track: Track, frames=None) -> Tracked:
+        """A clip whose first camera alone is known: ``spec`` holds one pose.  Frame 0 is integrated there; every later frame is tracked from the
+        previous frame's pose and integrated at the pose found; a lost frame keeps the previous pose and is not integrated.  ``depth`` and
+        ``frames`` as for ``integrate``, placed on the GPU once."""
+        with torch.cuda.device(self.device):
+            depth = _on_device(self._own(depth), self.device)
+            return _track_clip(self, depth, spec, track, None if frames is None else _on_device(frames, self.device))
 
 
 def _face_dtype():

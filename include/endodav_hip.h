@@ -520,6 +520,52 @@ int edv_tsdf_mesh_extract(const edv_tsdf_volume *vol, float min_weight, const vo
 int edv_tsdf_raycast(const edv_tsdf_volume *vol, const double *cams_dev, int32_t views, int32_t h, int32_t w, double near, double step, int32_t steps,
                      float min_weight, float *depth_dev, float *normals_dev, uint8_t *colors_dev, void *stream);
 
+/* ---- camera tracking against the fused surface (fusion.icp_sums, fusion.Tsdf.track, model.video_surface(track=...)) ----
+ * Additive entry points: the ABI version stays as it is.  One step of frame-to-model point-to-plane ICP: a live depth frame, lifted through the
+ * current estimate of its camera, is associated projectively with one view of edv_tsdf_raycast (the model's depth and normal maps seen from
+ * the previous pose), and the normal equations of the twist are summed over the pairs.  Nothing but sums_dev and the workspace is written.
+ * fusion.icp_sums_host is the numpy mirror, bit for bit.  Every multiply, add and divide below is rounded on its own.
+ * sel and frame: the cloud's selection and one frame of it, 0 <= frame < sel->n.  The output grid is the cloud's, oh = ceil(h/step),
+ *   ow = ceil(w/step); output pixel (oy, ox) samples the source pixel the selection names, and its z (fp32) and kept are the selection's.
+ * live_cam_host: 21 doubles in host memory, Kinv[3][3], R[3][3], t[3] of the CURRENT estimate (a row of cloud.Cloud.cams).
+ * model_cam_host: 39 doubles in host memory: the model view's own 21 as above (Kinv_m, R_m, t_m), then W[3][4] and K00 K01 K02 K10 K11 K12 of
+ *   edv_tsdf_integrate for the same camera.  Both arrays are read before the call returns and travel in the launch arguments: the live pose
+ *   changes with every iteration, and nothing is staged.
+ * model_depth_dev [mh][mw] fp32 and model_normals_dev [mh][mw][3] fp32: one view of edv_tsdf_raycast.
+ * Per kept output pixel, in fp64:
+ *     u = (ox + 0.5) * step;  v = (oy + 0.5) * step;  l_i = (Kinv[i][0]*u + Kinv[i][1]*v) + Kinv[i][2]
+ *     r_i = (R[i][0]*l_0 + R[i][1]*l_1) + R[i][2]*l_2;  rho_i = r_i * (double)z;  P_i = t_i + rho_i            (the cloud's point, kept in fp64)
+ *     q_i = ((W[i][0]*P_x + W[i][1]*P_y) + W[i][2]*P_z) + W[i][3];   skip unless q_2 > 0 (which also skips NaN)
+ *     um = ((K00*q_0 + K01*q_1) + K02*q_2) / q_2;  vm = ((K10*q_0 + K11*q_1) + K12*q_2) / q_2
+ *     skip unless um >= 0 && um < mw && vm >= 0 && vm < mh, tested in fp64 before any conversion;  px = (int)um, py = (int)vm
+ *     dm = model_depth[py][px];  skip unless dm > 0 (a miss is +0, NaN fails);  N = (double)model_normals[py][px][0..2]
+ *     skip unless (N_x*N_x + N_y*N_y) + N_z*N_z > 0
+ *     lm_i = (Kinv_m[i][0]*(px + 0.5) + Kinv_m[i][1]*(py + 0.5)) + Kinv_m[i][2];  rm_i = (R_m[i][0]*lm_0 + R_m[i][1]*lm_1) + R_m[i][2]*lm_2
+ *     V_i = t_m,i + rm_i * (double)dm;  D_i = V_i - P_i;  skip unless (D_x*D_x + D_y*D_y) + D_z*D_z <= max_dist2
+ *     e = (N_x*D_x + N_y*D_y) + N_z*D_z;  c = rho x N, each product rounded and then the difference: c_x = rho_y*N_z - rho_z*N_y, and so on
+ *     J = (c_x, c_y, c_z, N_x, N_y, N_z): the twist (rotation, then translation) is about the live camera centre, which keeps the system well
+ *     conditioned far from the world origin.
+ *   The pixel's 29 terms: J_j*J_k for j <= k, the upper triangle row-major (21); J_j*e (6); e*e; 1.0.  A pixel that is skipped, not kept or
+ *   past the grid contributes 29 times +0.0.
+ * The sums, in fp64, in a fixed order, with no atomics: tile b holds output pixels 256*b .. 256*b + 255 in row-major order, a wave 64
+ *   consecutive pixels.  Inside a wave a butterfly: for s = 32, 16, 8, 4, 2, 1 every lane x <- x + x[lane ^ s].  The tile's sum is
+ *   ((w0 + w1) + w2) + w3 of its four waves, written to the workspace as [tile][29].  A second launch adds, for each of the 29 values, the tiles
+ *   in index order starting from tile 0's value, and writes sums_dev[0..28].  sums_dev[28] is the number of pairs, sums_dev[27] their squared
+ *   residuals.  Every workspace slot that is read and all 29 outputs are written on every call: neither needs clearing, and the same input
+ *   gives the same bits on every call.
+ * edv_icp_tile_pixels(): 256.  edv_icp_workspace: 29 * 8 bytes per tile, ceil(oh*ow / 256) tiles, 8-byte aligned device memory; 0 for a shape
+ *   the call refuses.
+ * The model is addressed only after the range test above and the live frame only inside its grid: a guess that looks anywhere reads nothing
+ *   outside the arrays.
+ * Null required pointers, a selection the cloud refuses (step < 1 among them), frame outside [0, sel->n), mh or mw < 1, mh*mw >= 2^31, model
+ * maps not 4-byte aligned, a max_dist2 that is not finite or not >= 0, sums_dev not 8-byte aligned and a workspace that is missing, short or
+ * not 8-byte aligned return non-zero and launch nothing. */
+int32_t edv_icp_tile_pixels(void);
+size_t edv_icp_workspace(int32_t h, int32_t w, int32_t step);
+int edv_icp_sums(const edv_cloud_selection *sel, int64_t frame, const double *live_cam_host, const double *model_cam_host, const float *model_depth_dev,
+                 const float *model_normals_dev, int32_t mh, int32_t mw, double max_dist2, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
+                 void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
