@@ -205,6 +205,11 @@ int icp_tile_pixels();  // output pixels per workgroup, 29 * 8 workspace bytes e
 size_t icp_workspace(int h, int w, int step);  // bytes; 0 for a shape the call refuses
 int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
              double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream);
+// the same step with the frame's depth scale as a seventh unknown: the column J_6 = rho . N joins the six, 37 sums, 37 * 8 workspace bytes a tile;
+// the 29 values both have come out with the same bits
+size_t icp_scaled_workspace(int h, int w, int step);
+int icp_scaled_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh,
+                    int mw, double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

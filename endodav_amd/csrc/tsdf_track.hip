@@ -2,7 +2,9 @@
 // Camera tracking against the fused surface: the normal equations of one point-to-plane ICP step.  A live depth frame, lifted through the
 // current estimate of its camera, is associated projectively with one view of tsdf_raycast.hip (the model's depth and normal maps seen from the
 // previous pose), and the 6 x 6 system of the twist about the live camera centre is summed over the pairs.  The rule is stated once, in
-// include/endodav_hip.h; fusion.icp_sums_host is the mirror, bit for bit.
+// include/endodav_hip.h; fusion.icp_sums_host is the mirror, bit for bit.  With the frame's depth scale as a seventh unknown (icp_scaled_sums)
+// the column J_6 = rho . N joins the six and the system is 7 x 7: 37 terms instead of 29, the same kernels instantiated on the column count,
+// the same order of every sum, so the 29 values the two share come out with the same bits.
 //   icp_tile   one workgroup per tile of ICP_TILE output pixels of the cloud's grid in row-major order, one thread per pixel: the pixel's 29
 //              terms in fp64 (the upper triangle of J J^T, J e, e e and 1; 29 times +0 for a pixel without a pair), summed over the wave by a
 //              butterfly and over the four waves in wave order (common.hpp's block_sum_store), one row of 29 doubles per tile in the workspace
@@ -11,7 +13,7 @@
 // nothing is staged.  The model is addressed only after its pixel passed the range test in fp64, and the live frame only inside the grid, so a
 // guess that looks anywhere reads nothing outside the arrays.
 // No atomics, no workgroup waits for another, a fixed order of every addition: the same input gives the same bits on every call.  Every slot of
-// the workspace that is read and all 29 outputs are written on every call.  Contraction is off for the whole file and the division is IEEE's.
+// the workspace that is read and all 29 (37) outputs are written on every call.  Contraction is off for the whole file and the division is IEEE's.
 #include <cmath>
 
 #include "ops.hpp"
@@ -23,7 +25,8 @@ namespace {
 
 constexpr int ICP_THREADS = 256;
 constexpr int ICP_TILE = ICP_THREADS;  // output pixels per workgroup: the one constant behind icp_tile_pixels()
-constexpr int ICP_TERMS = 29;
+constexpr int icp_term_count(int cols) { return cols * (cols + 1) / 2 + cols + 2; }  // the upper triangle of J J^T, J e, e e and 1
+static_assert(icp_term_count(6) == 29 && icp_term_count(7) == 37);
 constexpr int ICP_TOTAL_THREADS = 64;
 
 struct IcpCams {
@@ -37,10 +40,11 @@ __device__ __forceinline__ void rows3(const double *M, double a, double b, doubl
     for (int i = 0; i < 3; ++i) o[i] = (M[3 * i] * a + M[3 * i + 1] * b) + M[3 * i + 2] * c;
 }
 
-// the 29 terms of output pixel q < grid_pixels of the live frame; false, with `a` untouched, for a pixel without a pair
+// the 29 (COLS = 6) or 37 (COLS = 7) terms of output pixel q < grid_pixels of the live frame; false, with `a` untouched, for a pixel without a pair
+template <int COLS>
 __device__ __forceinline__ bool icp_terms(const CloudSel &s, const IcpCams &c, const float *__restrict__ xf, const uint8_t *__restrict__ mf, int ow, unsigned q,
                                           const float *__restrict__ model_depth, const float *__restrict__ model_normals, int mh, int mw, double max_dist2,
-                                          double (&a)[ICP_TERMS]) {
+                                          double (&a)[icp_term_count(COLS)]) {
     int ox, oy;
     const int p = source_pixel(s, ow, q, ox, oy);
     float z;
@@ -77,54 +81,58 @@ __device__ __forceinline__ bool icp_terms(const CloudSel &s, const IcpCams &c, c
     for (int i = 0; i < 3; ++i) D[i] = (c.model[18 + i] + rm[i] * (double)dm) - P[i];
     if (!((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2] <= max_dist2)) return false;
     const double e = (N[0] * D[0] + N[1] * D[1]) + N[2] * D[2];
-    const double J[6] = {rho[1] * N[2] - rho[2] * N[1], rho[2] * N[0] - rho[0] * N[2], rho[0] * N[1] - rho[1] * N[0], N[0], N[1], N[2]};
+    double J[COLS] = {rho[1] * N[2] - rho[2] * N[1], rho[2] * N[0] - rho[0] * N[2], rho[0] * N[1] - rho[1] * N[0], N[0], N[1], N[2]};
+    if constexpr (COLS == 7) J[6] = (rho[0] * N[0] + rho[1] * N[1]) + rho[2] * N[2];  // the scale: P moves by delta * rho
+    constexpr int TRI = COLS * (COLS + 1) / 2;
     int t = 0;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
+    for (int j = 0; j < COLS; ++j) {
 #pragma unroll
-        for (int k = j; k < 6; ++k) a[t++] = J[j] * J[k];
+        for (int k = j; k < COLS; ++k) a[t++] = J[j] * J[k];
     }
 #pragma unroll
-    for (int j = 0; j < 6; ++j) a[21 + j] = J[j] * e;
-    a[27] = e * e;
-    a[28] = 1.0;
+    for (int j = 0; j < COLS; ++j) a[TRI + j] = J[j] * e;
+    a[TRI + COLS] = e * e;
+    a[TRI + COLS + 1] = 1.0;
     return true;
 }
 
-// grid: tiles.  tile_sums [tiles][29]
+// grid: tiles.  tile_sums [tiles][29] (COLS = 6) or [tiles][37] (COLS = 7)
+template <int COLS>
 __global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(CloudSel s, long long frame, IcpCams c, int ow, unsigned grid_pixels, const float *__restrict__ model_depth,
                                                                const float *__restrict__ model_normals, int mh, int mw, double max_dist2,
                                                                double *__restrict__ tile_sums) {
     const unsigned q = blockIdx.x * (unsigned)ICP_TILE + threadIdx.x;
-    double a[ICP_TERMS];
+    constexpr int TERMS = icp_term_count(COLS);
+    double a[TERMS];
     bool pair = false;
     if (q < grid_pixels) {
         const float *xf = s.x + frame * s.h * s.w;
         const uint8_t *mf = s.mask ? s.mask + frame * s.mask_stride : nullptr;
-        pair = icp_terms(s, c, xf, mf, ow, q, model_depth, model_normals, mh, mw, max_dist2, a);
+        pair = icp_terms<COLS>(s, c, xf, mf, ow, q, model_depth, model_normals, mh, mw, max_dist2, a);
     }
     if (!pair) {
 #pragma unroll
-        for (int j = 0; j < ICP_TERMS; ++j) a[j] = 0.0;
+        for (int j = 0; j < TERMS; ++j) a[j] = 0.0;
     }
     // every thread of the workgroup: a butterfly over each wave, then ((w0 + w1) + w2) + w3
-    block_sum_store<ICP_TERMS>(a, tile_sums + (size_t)blockIdx.x * ICP_TERMS);
+    block_sum_store<TERMS>(a, tile_sums + (size_t)blockIdx.x * TERMS);
 }
 
 // one workgroup: sums[j] = (((t_0 + t_1) + t_2) + ...)[j], tile by tile.  The loads of eight tiles are issued together; the additions keep their order.
-__global__ __launch_bounds__(ICP_TOTAL_THREADS) void icp_total_kernel(const double *__restrict__ tile_sums, unsigned tiles, double *__restrict__ sums) {
+__global__ __launch_bounds__(ICP_TOTAL_THREADS) void icp_total_kernel(const double *__restrict__ tile_sums, unsigned tiles, unsigned terms, double *__restrict__ sums) {
     const unsigned j = threadIdx.x;
-    if (j >= (unsigned)ICP_TERMS) return;
+    if (j >= terms) return;
     double t = tile_sums[j];
     unsigned i = 1;
     for (; i + 8 <= tiles; i += 8) {
         double v[8];
 #pragma unroll
-        for (unsigned k = 0; k < 8; ++k) v[k] = tile_sums[(size_t)(i + k) * ICP_TERMS + j];
+        for (unsigned k = 0; k < 8; ++k) v[k] = tile_sums[(size_t)(i + k) * terms + j];
 #pragma unroll
         for (unsigned k = 0; k < 8; ++k) t = t + v[k];
     }
-    for (; i < tiles; ++i) t = t + tile_sums[(size_t)i * ICP_TERMS + j];
+    for (; i < tiles; ++i) t = t + tile_sums[(size_t)i * terms + j];
     sums[j] = t;
 }
 
@@ -141,17 +149,17 @@ inline IcpGrid icp_grid(int h, int w, int step) {
     return {(int)ow, (unsigned)(oh * ow), (unsigned)((oh * ow + ICP_TILE - 1) / ICP_TILE)};
 }
 
-}  // namespace
-
-int icp_tile_pixels() { return ICP_TILE; }
-
-size_t icp_workspace(int h, int w, int step) {
+template <int COLS>
+size_t icp_workspace_of(int h, int w, int step) {
     if (!icp_shape_ok(h, w, step)) return 0;
-    return (size_t)icp_grid(h, w, step).tiles * ICP_TERMS * sizeof(double);
+    return (size_t)icp_grid(h, w, step).tiles * icp_term_count(COLS) * sizeof(double);
 }
 
-int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
-             double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
+template <int COLS>
+int icp_sums_of(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
+                double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
+    constexpr int TERMS = icp_term_count(COLS);
+    static_assert(TERMS <= ICP_TOTAL_THREADS, "one thread of the total per term");
     EDV_TRY(check_selection(s));
     EDV_CHECK(frame >= 0 && frame < s.n, "frame outside the clip");
     EDV_CHECK(live_cam && model_cam, "null cameras");
@@ -159,17 +167,35 @@ int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const d
     EDV_CHECK(mh >= 1 && mw >= 1 && (long long)mh * mw < (1ll << 31), "mh and mw must be at least 1 and the model view below 2^31 pixels");
     EDV_CHECK(std::isfinite(max_dist2) && max_dist2 >= 0.0, "max_dist2 must be finite and >= 0");
     EDV_CHECK(sums && aligned_to(sums, 8), "sums missing or not 8-byte aligned");
-    EDV_CHECK(ws && aligned_to(ws, 8) && ws_bytes >= icp_workspace(s.h, s.w, s.step), "workspace missing, too small or not 8-byte aligned (edv_icp_workspace)");
+    EDV_CHECK(ws && aligned_to(ws, 8) && ws_bytes >= icp_workspace_of<COLS>(s.h, s.w, s.step),
+              "workspace missing, too small or not 8-byte aligned (edv_icp_workspace, edv_icp_scaled_workspace)");
     const IcpGrid g = icp_grid(s.h, s.w, s.step);
     IcpCams c;
     for (int i = 0; i < 21; ++i) c.live[i] = live_cam[i];
     for (int i = 0; i < 39; ++i) c.model[i] = model_cam[i];
     double *tile_sums = static_cast<double *>(ws);
-    EDV_LAUNCH(icp_tile_kernel, dim3(g.tiles), dim3(ICP_THREADS), 0, stream, s, frame, c, g.ow, g.pixels, model_depth, model_normals, mh, mw, max_dist2, tile_sums);
+    EDV_LAUNCH(icp_tile_kernel<COLS>, dim3(g.tiles), dim3(ICP_THREADS), 0, stream, s, frame, c, g.ow, g.pixels, model_depth, model_normals, mh, mw, max_dist2, tile_sums);
     EDV_LAUNCH_OK();
-    EDV_LAUNCH(icp_total_kernel, dim3(1), dim3(ICP_TOTAL_THREADS), 0, stream, tile_sums, g.tiles, sums);
+    EDV_LAUNCH(icp_total_kernel, dim3(1), dim3(ICP_TOTAL_THREADS), 0, stream, tile_sums, g.tiles, (unsigned)TERMS, sums);
     EDV_LAUNCH_OK();
     return 0;
+}
+
+}  // namespace
+
+int icp_tile_pixels() { return ICP_TILE; }
+
+size_t icp_workspace(int h, int w, int step) { return icp_workspace_of<6>(h, w, step); }
+size_t icp_scaled_workspace(int h, int w, int step) { return icp_workspace_of<7>(h, w, step); }
+
+int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
+             double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
+    return icp_sums_of<6>(s, frame, live_cam, model_cam, model_depth, model_normals, mh, mw, max_dist2, sums, ws, ws_bytes, stream);
+}
+
+int icp_scaled_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh,
+                    int mw, double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
+    return icp_sums_of<7>(s, frame, live_cam, model_cam, model_depth, model_normals, mh, mw, max_dist2, sums, ws, ws_bytes, stream);
 }
 
 }  // namespace edv

@@ -857,7 +857,8 @@ class endodav(nn.Module):
         colour maps (``fusion.Tsdf.raycast``).
         ``track`` (a ``fusion.Track``): the video comes without poses.  ``spec`` then holds exactly one pose, the first camera's; every later
         frame is tracked against the volume from the previous frame's pose and integrated where it was found (``fusion.Tsdf.track_clip``), and
-        the call returns (the surface, a ``fusion.Tracked`` with the poses found), for every ``surface``."""
+        the call returns (the surface, a ``fusion.Tracked`` with the poses found), for every ``surface``.  With ``Track(scale=True)`` every
+        frame's depth scale is tracked with its pose and the frame is integrated at that scale; ``Tracked.scales`` holds the scales found."""
         from . import cloud, fusion
 
         if surface not in ("points", "mesh", "views"):

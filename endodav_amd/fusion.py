@@ -83,7 +83,7 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
             The depth is the cloud's: ``cloud.lift(depth, Cloud(K, pose, source="depth"))`` puts the hits back in the world.
 
   tracking  the pose of a frame found against the volume (``Track``, ``Tsdf.track`` / ``TsdfHost.track``, ``track_clip`` -> ``Tracked``;
-            ``edv_icp_sums``): frame-to-model point-to-plane ICP with projective association.  The volume is ray-cast once from the guess (one
+            ``edv_icp_sums``, ``edv_icp_scaled_sums``): frame-to-model point-to-plane ICP with projective association.  The volume is ray-cast once from the guess (one
             view with normals: the model); then ``iterations`` times the normal equations are summed on the GPU (``icp_sums``; ``icp_sums_host``
             is the mirror), solved on the host (``icp_solve``) and the twist applied (``apply_twist``).  Solve and twist are plain float64 numpy
             and the same functions for both classes, so a whole track differs only in where the sums came from.
@@ -110,9 +110,32 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
             clip      ``track_clip``: the Cloud holds one pose, the first camera's.  Frame 0 is integrated there; each later frame is tracked from
                       the previous frame's pose and integrated at the pose found; a lost frame keeps the previous pose and is not integrated.
             A scene that is a plane leaves sliding inside the plane unobservable; that is not detected.
+            scale     ``Track(scale=True)`` (``edv_icp_scaled_sums``): monocular depth is fixed only up to a scale that wanders from frame to
+                      frame, and a tracker that takes every frame in the volume's unit trades that scale for rotation and translation.  With the
+                      option the frame's scale is a seventh unknown.  Off (the default), everything above is unchanged to the bit.
+                      where     the scale is the Cloud's ``gain``, the one place the depth rule has for it.  For a scale factor sigma (a Python
+                                float) the frame is read with gain32 = float32(spec.gain * sigma), the product formed in Python doubles and rounded
+                                once, as ``Cloud.scalars()`` does: z (float32) and kept are the cloud's for that gain, near and far applied to the
+                                scaled depth.  The sums take no new scalar, and ``integrate`` sees exactly the z the tracker saw.
+                      pixel     up to e and J_0..J_5 the rule above, character for character.  The seventh column, float64, every operation
+                                rounded on its own:  J_6 = (rho_x*N_x + rho_y*N_y) + rho_z*N_z.  Growing the scale by delta moves P by delta*rho,
+                                so e falls by delta*J_6: the sign convention of the translation columns.
+                      terms     37 a pixel: [0..27] J_j*J_k for 0 <= j <= k <= 6, the upper triangle row-major; [28..34] J_j*e, j = 0..6; [35] e*e;
+                                [36] 1.  A pixel without a pair contributes 37 times +0.
+                      sums      exactly as above: tiles of 256, a butterfly per wave, ((w0 + w1) + w2) + w3, the tiles in index order from tile
+                                0's value.  The 29 values the 6-column sums also have come out with the same bits for the same inputs.
+                      solve     the symmetric 7 x 7 system by ``np.linalg.solve``, x = (rotation vector, translation, delta); lost as above.
+                      update    T <- apply_twist(T, x[:6]), then sigma <- sigma * (1.0 + x[6]).  The frame is also lost when sigma is not finite
+                                and positive, or when sigma / sigma_guess leaves [1/(1+m), 1+m] with m = ``Track.max_scale_step``.  A lost frame
+                                returns its guess, pose and scale factor 1.0.  After the last step R is re-orthonormalised as above.
+                      clip      frame 0 fixes the gauge, sigma_0 = 1.  Frame i is tracked from the previous frame's pose and scale: its Cloud
+                                carries gain = spec.gain * sigma_{i-1} and the factor starts at 1;  sigma_i = sigma_{i-1} * factor;  it is
+                                integrated with gain = spec.gain * sigma_i at the pose found.  A lost frame keeps the previous pose and scale and
+                                is not integrated.  ``Tracked.scales`` holds sigma_i.
 
-What is not built: hashed or sparse volumes, shading, free-space skipping, and in the tracker image pyramids, compatibility tests between live and
-model normals, robust weights, loop closure and relocalisation after a lost frame."""
+What is not built: hashed or sparse volumes, shading, free-space skipping, and in the tracker an affine correction in disparity (scale and shift;
+the scale alone is ``Track(scale=True)``), image pyramids, compatibility tests between live and model normals, robust weights, loop closure and
+relocalisation after a lost frame."""
 from __future__ import annotations
 
 import ctypes as C
@@ -378,6 +401,8 @@ def _staged(a: np.ndarray, dev: torch.device) -> torch.Tensor:
 
 # ---- tracking -------------------------------------------------------------------------------------------------------------------------------
 ICP_TERMS = 29   # the upper triangle of J J^T (21), J e (6), e e, and the count
+ICP_SCALED_TERMS = 37   # with the scale as a seventh column: 28, 7, e e, and the count
+_ICP_COLS = {ICP_TERMS: 6, ICP_SCALED_TERMS: 7}
 ICP_TILE = 256   # output pixels per tile of the ordered sum: edv_icp_tile_pixels()
 _LANE = np.arange(64)
 
@@ -397,8 +422,15 @@ class Track:
     max_dist: float = None                   # pairs farther apart than this are dropped; None = the volume's trunc
     min_pairs: int = 64                      # fewer pairs than this: the frame is lost
     min_weight: float = 1.0                  # of the ray-cast
+    scale: bool = False                      # the frame's depth scale is a seventh unknown (module docstring, "scale")
+    max_scale_step: float = 0.25             # with ``scale``: a frame whose scale leaves [1/(1+m), 1+m] times its guess is lost
 
     def __post_init__(self):
+        if not isinstance(self.scale, bool):
+            raise ValueError(f"scale must be True or False, got {self.scale!r}")
+        if not _positive(self.max_scale_step):
+            raise ValueError(f"max_scale_step must be finite and positive, got {self.max_scale_step!r}")
+        object.__setattr__(self, "max_scale_step", float(self.max_scale_step))
         for name in ("near", "far"):
             if not _number(getattr(self, name)):
                 raise ValueError(f"{name} must be a finite number, got {getattr(self, name)!r}")
@@ -431,6 +463,7 @@ class Tracked:
     pairs: np.ndarray                        # int64 [n], the pairs of the last ICP step; 0 for frame 0
     rms: np.ndarray                          # float64 [n], the root mean square point-to-plane distance of those pairs; 0 for frame 0
     lost: np.ndarray                         # bool [n]; a lost frame is not integrated
+    scales: np.ndarray = None                # float64 [n] with ``Track(scale=True)``: sigma_i relative to ``spec.gain``, 1.0 for frame 0; a lost frame repeats the previous one.  None otherwise
 
 
 def _check_icp(depth, spec, model, views, max_dist, frame):
@@ -466,13 +499,14 @@ def _live_cam(kinv9, T) -> np.ndarray:
 
 
 def _ordered_sum(terms: np.ndarray) -> np.ndarray:
-    """float64 [p, 29] per output pixel in row-major order -> [29], added in the kernel's order: tiles of 256 pixels, a wave 64 of them; a
+    """float64 [p, 29] (or [p, 37]) per output pixel in row-major order -> [29] (or [37]), added in the kernel's order: tiles of 256 pixels, a wave 64 of them; a
     butterfly inside the wave, the four waves in order, then the tiles in order, starting from tile 0's value."""
     p = terms.shape[0]
     tiles = -(-p // ICP_TILE)
-    x = np.zeros((tiles * ICP_TILE, ICP_TERMS))
+    count = terms.shape[1]
+    x = np.zeros((tiles * ICP_TILE, count))
     x[:p] = terms
-    x = x.reshape(tiles, ICP_TILE // 64, 64, ICP_TERMS)
+    x = x.reshape(tiles, ICP_TILE // 64, 64, count)
     for s in (32, 16, 8, 4, 2, 1):
         x = x + x[:, :, _LANE ^ s, :]
     wave = x[:, :, 0, :]
@@ -487,34 +521,42 @@ class _IcpHost:
     """One live frame against one model view in numpy: what does not depend on the estimate is formed once."""
     output = "host"
 
-    def __init__(self, depth, spec, model, views, max_dist, frame):
+    def __init__(self, depth, spec, model, views, max_dist, frame, scale=False):
         depth = np.asarray(depth)
         n, h, w, mask, cams, self.model_cam = _check_icp(depth, spec, model, views, max_dist, frame)
+        self.cols = 7 if scale else 6
         self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
         self.max_dist2 = float(max_dist) * float(max_dist)
         step = int(spec.step)
         oh, ow = -(-h // step), -(-w // step)
         sy = np.minimum(np.arange(oh, dtype=np.int64) * step + step // 2, h - 1)
         sx = np.minimum(np.arange(ow, dtype=np.int64) * step + step // 2, w - 1)
-        lo, span, gain, near, far = spec.scalars()
-        x = depth[frame][sy][:, sx]
+        self.source, self.scalars = spec.source, spec.scalars()
+        self.x = depth[frame][sy][:, sx]
+        self.unmasked = None if mask is None else (mask[frame] if mask.ndim == 3 else mask)[sy][:, sx] != 0
+        self.set_gain(self.scalars[2])
+        self.u = np.broadcast_to(((np.arange(ow, dtype=np.float64) + 0.5) * float(step))[None, :], (oh, ow)).reshape(-1)
+        self.v = np.broadcast_to(((np.arange(oh, dtype=np.float64) + 0.5) * float(step))[:, None], (oh, ow)).reshape(-1)
+        self.depth, self.normals = np.asarray(model.depth)[0], np.asarray(model.normals)[0]
+
+    def set_gain(self, gain) -> None:
+        """z and kept of the frame again, in float32, for the float32 ``gain``: the cloud's depth rule."""
+        lo, span, _, near, far = self.scalars
+        gain, x = np.float32(gain), self.x
         with np.errstate(all="ignore"):
-            if spec.source == "depth":
+            if self.source == "depth":
                 z = x * gain
             else:
                 scaled = lo + span * x
                 z = np.float32(1.0) / scaled
                 z = z * gain
             keep = (z > near) & (z < far)
-        if mask is not None:
-            keep &= (mask[frame] if mask.ndim == 3 else mask)[sy][:, sx] != 0
+        if self.unmasked is not None:
+            keep &= self.unmasked
         self.z, self.keep = z.astype(np.float64).reshape(-1), keep.reshape(-1)
-        self.u = np.broadcast_to(((np.arange(ow, dtype=np.float64) + 0.5) * float(step))[None, :], (oh, ow)).reshape(-1)
-        self.v = np.broadcast_to(((np.arange(oh, dtype=np.float64) + 0.5) * float(step))[:, None], (oh, ow)).reshape(-1)
-        self.depth, self.normals = np.asarray(model.depth)[0], np.asarray(model.normals)[0]
 
     def terms(self, live: np.ndarray) -> np.ndarray:
-        """float64 [oh * ow, 29]: the terms of every output pixel for the estimate ``live`` (21 doubles), +0 where there is no pair."""
+        """float64 [oh * ow, 29 or 37]: the terms of every output pixel for the estimate ``live`` (21 doubles), +0 where there is no pair."""
         kinv, rot, pos = live[:9].reshape(3, 3), live[9:18].reshape(3, 3), live[18:]
         m = self.model_cam
         kinv_m, rot_m, pos_m, W, K = m[:9].reshape(3, 3), m[9:18].reshape(3, 3), m[18:21], m[21:33].reshape(3, 4), m[33:].reshape(2, 3)
@@ -542,7 +584,10 @@ class _IcpHost:
             ok &= (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2] <= self.max_dist2
             e = (N[0] * D[0] + N[1] * D[1]) + N[2] * D[2]
             J = [rho[1] * N[2] - rho[2] * N[1], rho[2] * N[0] - rho[0] * N[2], rho[0] * N[1] - rho[1] * N[0], N[0], N[1], N[2]]
-            cols = [J[j] * J[k] for j in range(6) for k in range(j, 6)] + [J[j] * e for j in range(6)] + [e * e, np.ones_like(e)]
+            if self.cols == 7:
+                J.append((rho[0] * N[0] + rho[1] * N[1]) + rho[2] * N[2])
+            m = self.cols
+            cols = [J[j] * J[k] for j in range(m) for k in range(j, m)] + [J[j] * e for j in range(m)] + [e * e, np.ones_like(e)]
             return np.stack([np.where(ok, c, 0.0) for c in cols], axis=1)
 
     def sums(self, live: np.ndarray) -> np.ndarray:
@@ -550,11 +595,11 @@ class _IcpHost:
 
 
 class _IcpDevice:
-    """The same on the GPU (``edv_icp_sums``): the clip, the mask, the model and the workspace are placed once, an estimate costs two launches
-    and one 232-byte read, for which the host waits."""
+    """The same on the GPU (``edv_icp_sums``, or ``edv_icp_scaled_sums`` with ``scale``): the clip, the mask, the model and the workspace are
+    placed once, an estimate costs two launches and one read of 232 (296) bytes, for which the host waits."""
     output = "device"
 
-    def __init__(self, depth, spec, model, views, max_dist, frame, device=None):
+    def __init__(self, depth, spec, model, views, max_dist, frame, device=None, scale=False):
         if isinstance(depth, torch.Tensor):
             if not depth.is_cuda:
                 raise ValueError("a depth tensor must live on the GPU (pass host data as a numpy array)")
@@ -565,6 +610,9 @@ class _IcpDevice:
         if device is None:
             device = model.depth.device if isinstance(model.depth, torch.Tensor) and model.depth.is_cuda else torch.device("cuda", torch.cuda.current_device())
         self.device, self.frame, self.lib = device, int(frame), _lib.load()
+        self.name = "edv_icp_scaled_sums" if scale else "edv_icp_sums"
+        self.entry, workspace = getattr(self.lib, self.name), self.lib.edv_icp_scaled_workspace if scale else self.lib.edv_icp_workspace
+        count = ICP_SCALED_TERMS if scale else ICP_TERMS
         self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
         self.max_dist2 = float(max_dist) * float(max_dist)
         self.model_cam = (C.c_double * 39)(*model_cam)
@@ -574,16 +622,20 @@ class _IcpDevice:
             self.mask = None if mask is None else _staged(mask, device)
             self.sel = selection(self.x, spec, self.mask)
             self.depth, self.normals = _on_device(model.depth, device), _on_device(model.normals, device)
-            self.ws = torch.empty(max(int(self.lib.edv_icp_workspace(h, w, int(spec.step))), 8), dtype=torch.uint8, device=device)
-            self.sums_d = torch.empty(ICP_TERMS, dtype=torch.float64, device=device)
-            self.sums_h = torch.empty(ICP_TERMS, dtype=torch.float64, pin_memory=True)
+            self.ws = torch.empty(max(int(workspace(h, w, int(spec.step))), 8), dtype=torch.uint8, device=device)
+            self.sums_d = torch.empty(count, dtype=torch.float64, device=device)
+            self.sums_h = torch.empty(count, dtype=torch.float64, pin_memory=True)
+
+    def set_gain(self, gain) -> None:
+        """The ``gain`` field of the selection struct rewritten with the float32 ``gain``: the struct travels by value with every launch."""
+        self.sel.gain = float(np.float32(gain))
 
     def sums(self, live: np.ndarray) -> np.ndarray:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            _lib.check(self.lib.edv_icp_sums(C.byref(self.sel), self.frame, (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(), self.normals.data_ptr(),
-                                             self.size[0], self.size[1], self.max_dist2, self.sums_d.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
-                                             C.c_void_p(stream.cuda_stream)), "edv_icp_sums")
+            _lib.check(self.entry(C.byref(self.sel), self.frame, (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(), self.normals.data_ptr(),
+                                  self.size[0], self.size[1], self.max_dist2, self.sums_d.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                  C.c_void_p(stream.cuda_stream)), self.name)
             self.sums_h.copy_(self.sums_d, non_blocking=True)
             stream.synchronize()
             return self.sums_h.numpy().copy()
@@ -593,31 +645,41 @@ def _estimate(ctx, spec: Cloud, frame: int) -> np.ndarray:
     return _live_cam(ctx.kinv, _pose4(spec.pose[frame if spec.pose.shape[0] > 1 else 0]))
 
 
-def icp_sums(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0) -> np.ndarray:
-    """float64 [29]: the sums of one point-to-plane step (module docstring, "tracking") between frame ``frame`` of ``depth`` (float32 [n, h, w], a
+def _check_scale(scale) -> bool:
+    if not isinstance(scale, (bool, np.bool_)):
+        raise ValueError(f"scale must be True or False, got {scale!r}")
+    return bool(scale)
+
+
+def icp_sums(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0, scale: bool = False) -> np.ndarray:
+    """float64 [29], or [37] with ``scale`` (the seventh column, for the scale ``spec.gain`` holds): the sums of one point-to-plane step (module docstring, "tracking") between frame ``frame`` of ``depth`` (float32 [n, h, w], a
     numpy array or a tensor on the GPU, as for ``Tsdf.integrate``), lifted through ``spec`` whose pose is the estimate, and ``model``, a one-view
     ``Raycast`` with normals (arrays or tensors) cast from ``views``.  On the GPU, on the caller's current stream; the host waits for the result."""
-    ctx = _IcpDevice(depth, spec, model, views, max_dist, frame)
+    ctx = _IcpDevice(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale))
     return ctx.sums(_estimate(ctx, spec, frame))
 
 
-def icp_sums_host(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0) -> np.ndarray:
+def icp_sums_host(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0, scale: bool = False) -> np.ndarray:
     """``icp_sums`` in numpy, the same operations in the same order: the two agree bit for bit."""
-    ctx = _IcpHost(depth, spec, model, views, max_dist, frame)
+    ctx = _IcpHost(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale))
     return ctx.sums(_estimate(ctx, spec, frame))
 
 
 def icp_solve(sums, min_pairs):
-    """The twist xi [6] (rotation vector, then translation) of the normal equations in ``sums``, or None when the frame is lost: fewer than
-    ``min_pairs`` pairs, a singular system, or a solution that is not finite."""
+    """The twist xi [6] (rotation vector, then translation) of the normal equations in the 29 ``sums``, or x [7] (the twist, then the scale's
+    delta) of the 37, or None when the frame is lost: fewer than ``min_pairs`` pairs, a singular system, or a solution that is not finite."""
     sums = np.asarray(sums, dtype=np.float64)
-    if not sums[28] >= min_pairs:
+    if sums.shape not in ((ICP_TERMS,), (ICP_SCALED_TERMS,)):
+        raise ValueError(f"expected {ICP_TERMS} or {ICP_SCALED_TERMS} sums, got shape {tuple(sums.shape)}")
+    m = _ICP_COLS[sums.shape[0]]
+    tri = m * (m + 1) // 2
+    if not sums[-1] >= min_pairs:
         return None
-    A = np.zeros((6, 6))
-    A[np.triu_indices(6)] = sums[:21]
+    A = np.zeros((m, m))
+    A[np.triu_indices(m)] = sums[:tri]
     A = A + np.triu(A, 1).T
     try:
-        xi = np.linalg.solve(A, sums[21:27])
+        xi = np.linalg.solve(A, sums[tri:tri + m])
     except np.linalg.LinAlgError:
         return None
     return xi if np.isfinite(xi).all() else None
@@ -645,19 +707,26 @@ def _track(tsdf, context, depth, spec, track, frame):
     guess = _pose4(spec.pose[frame if spec.pose.shape[0] > 1 else 0])
     views = track.views(spec.K[frame if spec.K.shape[0] > 1 else 0], guess, (h, w))
     model = tsdf.raycast(views, min_weight=track.min_weight, normals=True, output=context.output)
-    ctx = context(depth, spec, model, views, tsdf.volume.trunc if track.max_dist is None else track.max_dist, frame)
-    T, pairs, rms = guess.copy(), 0, float("nan")
+    ctx = context(depth, spec, model, views, tsdf.volume.trunc if track.max_dist is None else track.max_dist, frame, scale=track.scale)
+    T, pairs, rms, sigma = guess.copy(), 0, float("nan"), 1.0
+    lost = (guess, 1.0) if track.scale else (guess,)
     for _ in range(track.iterations):
+        if track.scale:
+            ctx.set_gain(np.float32(float(spec.gain) * sigma))
         sums = ctx.sums(_live_cam(ctx.kinv, T))
-        pairs = int(sums[28])
-        rms = math.sqrt(sums[27] / sums[28]) if sums[28] > 0.0 else float("nan")
+        pairs = int(sums[-1])
+        rms = math.sqrt(sums[-2] / sums[-1]) if sums[-1] > 0.0 else float("nan")
         xi = icp_solve(sums, track.min_pairs)
         if xi is None:
-            return guess, pairs, rms, True
-        T = apply_twist(T, xi)
+            return lost[0], pairs, rms, True, *lost[1:]
+        T = apply_twist(T, xi[:6])
+        if track.scale:
+            sigma = sigma * (1.0 + float(xi[6]))
+            if not (math.isfinite(sigma) and sigma > 0.0 and 1.0 / (1.0 + track.max_scale_step) <= sigma <= 1.0 + track.max_scale_step):
+                return lost[0], pairs, rms, True, *lost[1:]
     U, _, Vt = np.linalg.svd(T[:3, :3])
     T[:3, :3] = U @ Vt
-    return T, pairs, rms, False
+    return (T, pairs, rms, False, sigma) if track.scale else (T, pairs, rms, False)
 
 
 def _track_clip(tsdf, depth, spec, track, frames):
@@ -667,16 +736,23 @@ def _track_clip(tsdf, depth, spec, track, frames):
     n, h, w, _, mask = _check_integrate(depth, spec, frames, tsdf.coloured)
     if spec.pose.shape[0] != 1:
         raise ValueError(f"tracking starts from one pose, the first camera's; the Cloud holds {spec.pose.shape[0]}")
-    out = Tracked(np.zeros((n, 4, 4)), np.zeros(n, np.int64), np.zeros(n), np.zeros(n, bool))
-    T = _pose4(spec.pose[0])
+    out = Tracked(np.zeros((n, 4, 4)), np.zeros(n, np.int64), np.zeros(n), np.zeros(n, bool), np.ones(n) if track.scale else None)
+    T, sigma = _pose4(spec.pose[0]), 1.0
     for i in range(n):
         one = dataclasses.replace(spec, K=spec.K[i if spec.K.shape[0] > 1 else 0], pose=T, mask=mask[i] if mask is not None and mask.ndim == 3 else mask)
+        if track.scale:
+            one = dataclasses.replace(one, gain=float(spec.gain) * sigma)     # the previous frame's scale: the guess
         if i:
-            found, out.pairs[i], out.rms[i], out.lost[i] = tsdf.track(depth[i:i + 1], one, track)
+            found, out.pairs[i], out.rms[i], out.lost[i], *factor = tsdf.track(depth[i:i + 1], one, track)
             if not out.lost[i]:
                 T = found
                 one = dataclasses.replace(one, pose=T)
+                if track.scale:
+                    sigma = sigma * factor[0]
+                    one = dataclasses.replace(one, gain=float(spec.gain) * sigma)
         out.poses[i] = T
+        if track.scale:
+            out.scales[i] = sigma
         if not out.lost[i]:
             tsdf.integrate(depth[i:i + 1], one, None if frames is None else frames[i:i + 1])
     return out
@@ -917,7 +993,7 @@ class TsdfHost:
         return shaped
 
     def track(self, depth, spec: Cloud, track: Track, frame: int = 0):
-        """The mirror of ``Tsdf.track``: the same host code around ``icp_sums_host``."""
+        """The mirror of ``Tsdf.track``: the same host code around ``icp_sums_host``; a 5-tuple that ends with the scale factor with ``track.scale``."""
         return _track(self, _IcpHost, np.asarray(depth), spec, track, frame)
 
     def track_clip(self, depth, spec: Cloud, track: Track, frames=None) -> Tracked:
@@ -1089,13 +1165,15 @@ class Tsdf:
         """The pose of frame ``frame`` of ``depth`` (as for ``integrate``) against this volume (module docstring, "tracking"): the volume ray-cast
         once from the guess, which is ``spec.pose`` with ``spec.K`` and the frame's size, then ``track.iterations`` steps of sums on the GPU, a
         6 x 6 solve on the host and the twist applied.  Returns (T_world_camera float64 [4, 4], pairs, rms, lost); a lost frame returns the
-        guess.  On the caller's current stream; the host waits once per step."""
+        guess.  With ``track.scale`` the system is 7 x 7 and the tuple ends with the scale factor found, a Python float relative to
+        ``spec.gain``, 1.0 for a lost frame.  On the caller's current stream; the host waits once per step."""
         with torch.cuda.device(self.device):
             return _track(self, _IcpDevice, self._own(depth), spec, track, frame)
 
     def track_clip(self, depth, spec: Cloud, track: Track, frames=None) -> Tracked:
         """A clip whose first camera alone is known: ``spec`` holds one pose.  Frame 0 is integrated there; every later frame is tracked from the
-        previous frame's pose and integrated at the pose found; a lost frame keeps the previous pose and is not integrated.  ``depth`` and
+        previous frame's pose (with ``track.scale`` also from its scale, and integrated with the scale found: ``Tracked.scales``) and integrated at
+        the pose found; a lost frame keeps the previous pose and is not integrated.  ``depth`` and
         ``frames`` as for ``integrate``, placed on the GPU once."""
         with torch.cuda.device(self.device):
             depth = _on_device(self._own(depth), self.device)

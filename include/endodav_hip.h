@@ -566,6 +566,34 @@ int edv_icp_sums(const edv_cloud_selection *sel, int64_t frame, const double *li
                  const float *model_normals_dev, int32_t mh, int32_t mw, double max_dist2, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
                  void *stream);
 
+/* ---- the same step with the frame's depth scale as a seventh unknown (fusion.Track(scale=True), fusion.icp_sums(..., scale=True)) ----
+ * Additive entry points: the ABI version stays as it is.  Monocular depth is fixed only up to a scale that wanders from frame to frame; a
+ * tracker that takes every frame's depth in the volume's unit trades that scale for rotation and translation.  Here the scale is estimated
+ * with the pose.
+ * Where the scale lives: in the selection's gain, the one place the depth rule has for it.  For a scale factor sigma (a double on the host) the
+ *   frame is read with gain = (float)(spec.gain * sigma), the product formed in doubles and rounded once, so z (fp32) and kept are the
+ *   selection's for that gain, near and far applied to the scaled depth.  The call takes no new scalar, and edv_tsdf_integrate with the same
+ *   gain sees exactly the z the tracker saw.
+ * Per kept output pixel everything up to e and J_0..J_5 is edv_icp_sums' rule above, character for character.  The seventh column, in fp64,
+ *   every operation rounded on its own:
+ *     J_6 = (rho_x*N_x + rho_y*N_y) + rho_z*N_z
+ *   Growing the scale by delta moves P by delta*rho, so e falls by delta*J_6: the sign convention of the translation columns.
+ *   The pixel's 37 terms: [0..27] J_j*J_k for 0 <= j <= k <= 6, the upper triangle row-major; [28..34] J_j*e for j = 0..6; [35] e*e; [36] 1.0.
+ *   A pixel without a pair contributes 37 times +0.0.
+ * The sums exactly as above: tiles of 256 output pixels, a butterfly per wave, ((w0 + w1) + w2) + w3 to the workspace as [tile][37], then the
+ *   tiles in index order from tile 0's value into sums_dev[0..36]; fp64, no atomics.  The 29 values that edv_icp_sums also has (the triangle's
+ *   entries with k <= 5, [28..33], [35], [36]) come out with the same bits as it gives for the same inputs.  Every workspace slot that is read
+ *   and all 37 outputs are written on every call.
+ * On the host (fusion._track): x = (rotation vector, translation, delta) of the symmetric 7 x 7 system; T <- twist(T, x[0..5]);
+ *   sigma <- sigma * (1.0 + x[6]).  The frame is lost as above, and also when sigma is not finite and positive or sigma / sigma_guess leaves
+ *   [1/(1+m), 1+m], m = Track.max_scale_step.  A lost frame returns its guess, pose and factor 1.0.
+ * edv_icp_scaled_workspace: 37 * 8 bytes per tile, 0 for a shape the call refuses.  edv_icp_scaled_sums: the arguments and the refusals of
+ *   edv_icp_sums; it writes sums_dev[0..36]. */
+size_t edv_icp_scaled_workspace(int32_t h, int32_t w, int32_t step);
+int edv_icp_scaled_sums(const edv_cloud_selection *sel, int64_t frame, const double *live_cam_host, const double *model_cam_host, const float *model_depth_dev,
+                        const float *model_normals_dev, int32_t mh, int32_t mw, double max_dist2, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
+                        void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
