@@ -626,13 +626,14 @@ int trainer_loss(const TrainerLossIn &in, int N, int H, int W, const TrainerLoss
         EDV_LAUNCH_OK();
         // ---- gradients.  The kernels above produced d(loss_s)/d(.) for refined, transform_high and the warped images; total = mean over scales -> x 0.25 ----
         if (do_dr || do_df) EDV_HIP(hipMemsetAsync(gdep, 0, (size_t)N * P * sizeof(float), st));
-        const int gb = pose ? POSE_BLOCKS : pix_blocks;
-        if (pose && do_dr)
+        // With the depth-reprojection term on there is ONE instantiation, whoever requires grad: compiled without the pose sums the same arithmetic is
+        // contracted differently and the disparity gradients of a frozen-pose call moved by 1.2e-6 of scale against the all-leaves call
+        // (profiles/loss_edges_notes.txt).  The pose partials then go to the workspace and are not finished.
+        const int gb = (pose || do_dr) ? POSE_BLOCKS : pix_blocks;
+        if (do_dr)
             EDV_LAUNCH((geom_bwd_kernel<true, true>), dim3(gb, N), dim3(256), 0, st, D, in.color_nb[0], in.color_nb[1], cams, gx, drp_tot, gdg, gdep, pose_part, N, H, W, da, db, w_dr);
         else if (pose)
             EDV_LAUNCH((geom_bwd_kernel<true, false>), dim3(gb, N), dim3(256), 0, st, D, in.color_nb[0], in.color_nb[1], cams, gx, drp_tot, gdg, gdep, pose_part, N, H, W, da, db, w_dr);
-        else if (do_dr)
-            EDV_LAUNCH((geom_bwd_kernel<false, true>), dim3(gb, N), dim3(256), 0, st, D, in.color_nb[0], in.color_nb[1], cams, gx, drp_tot, gdg, gdep, pose_part, N, H, W, da, db, w_dr);
         else
             EDV_LAUNCH((geom_bwd_kernel<false, false>), dim3(gb, N), dim3(256), 0, st, D, in.color_nb[0], in.color_nb[1], cams, gx, drp_tot, gdg, gdep, pose_part, N, H, W, da, db, w_dr);
         EDV_LAUNCH_OK();
