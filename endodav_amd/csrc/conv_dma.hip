@@ -7,7 +7,7 @@
 // ds_write: per k-tile a lane issues its DMAs with one 64-bit select each.  The pre-activation ReLU of the
 // ResidualConvUnits is applied to the A fragments after the LDS read (4 v_max per 4 MFMAs).
 //
-// LDS image, swizzle and pipeline are those of gemm_dma.hip.  Tiles: 64x64 (2x2 waves) or, for Cout <= 32, 128x32 (4x1).
+// LDS image, swizzle and pipeline are those of gemm_dma.hip (dma_tile.hpp).  Tiles: 64x64 (2x2 waves) or, for Cout <= 32, 128x32 (4x1).
 //
 // Round 2 (BUF = true, operands within 4 GB): the k loop of gemm_dma.hip -- DMA through buffer descriptors with the tap / channel advance
 // in the SCALAR offset, scalar wave index, loop unrolled by two so that the LDS stage is an immediate -- because the f32 MFMA and the
@@ -19,12 +19,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm_common.hpp"
+#include "dma_tile.hpp"
 
 namespace edv {
 namespace {
 
-constexpr int CBK = 32;
+constexpr int CBK = TILE_BK;
 __device__ __attribute__((aligned(256))) float g_zero_page[64];
 
 // SPLIT: the stream-K scheme of streamk_plan.hpp / gemm_common.hpp for grids that do not fill the part (tiles <= resident workgroups, e.g. layer4_rn: 46
@@ -52,12 +52,11 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
     const float *zero = g_zero_page + spos * 4;
     const int opix = g.cOH * g.cOW;
     const int nkt = g.K / CBK;
-    const int ra = wm * 32 + l31, rb = wn * 32 + l31;
-    const int swa = (ra >> 1) & 7, swb = (rb >> 1) & 7;
 
-    // SPLIT: run `bid` of the split (stride 1: every workgroup of the grid owns one); plain: one whole tile
-    long long u = SPLIT ? (long long)bid * sp.chunk : 0;
-    const long long u_end = SPLIT ? (u + sp.chunk < sp.units ? u + sp.chunk : sp.units) : 0;
+    // SPLIT: the workgroup's run of the split (these plans have no whole rounds and stride 1: run `bid`); plain: one whole tile
+    const int run = split_run(sp, SPLIT, bid);
+    long long u = split_run_begin(sp, run);
+    const long long u_end = split_run_end(sp, run, u);
     bool once = true;
     for (;;) {
         int tile, kt0, kt1, lt = 0;
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
             const long long left = u_end - u;
             kt1 = kt0 + left < nkt ? kt0 + (int)left : nkt;
             tile = lt;
-            if (!(kt0 == 0 && kt1 == nkt)) part = split_slot<SPLIT_SLOT>(sp, bid, u);  // a piece: not the tile's whole k range
+            if (!(kt0 == 0 && kt1 == nkt)) part = split_slot<SPLIT_SLOT>(sp, run, u);  // a piece: not the tile's whole k range
             u += kt1 - kt0;
         } else {
             if (!once) break;
@@ -89,6 +88,7 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
 #pragma unroll
         for (int i = 0; i < IA; ++i) {
             const int r = (BM / 4) * wave + 8 * i + srow;
+            // (tile_chunk / tile_edge_row of dma_tile.hpp, written out here and below: as calls they change the k loop of four instantiations)
             const int c = spos ^ ((r >> 1) & 7);  // logical 16-byte chunk that lives at this LDS position
             long long m = m0 + r;
             m = m < g.M ? m : g.M - 1;  // rows past the edge read a valid pixel; their results are never stored
@@ -168,8 +168,8 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
         const float *fpa[4], *fpb[4];  // fragment read addresses in stage 0
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            fpa[q] = smem + ra * CBK + (((2 * q + lh) ^ swa) << 2);
-            fpb[q] = smem + BM * CBK + rb * CBK + (((2 * q + lh) ^ swb) << 2);
+            fpa[q] = tile_frag_ptr(smem, wm * 32 + l31, q, lh);
+            fpb[q] = tile_frag_ptr(smem + BM * CBK, wn * 32 + l31, q, lh);
         }
 
         EpiCols<1> cols;
@@ -192,34 +192,15 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
 
+        // tile_k_loop of dma_tile.hpp, written out (called as the shared function it moves the blocks of conv3_dma_kernel<4, 0, false, true>:
+        // profiles/dma_tile_refactor_notes.txt); one uniform prelu branch per k-tile
         issue(kt0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         auto ktile = [&](int kt, auto st_tag) {
             constexpr int ST = decltype(st_tag)::value;
             if (kt + 1 < kt1) issue(kt + 1, ST ^ 1);
-            f32x4 fa[4], fb[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                fa[q] = *reinterpret_cast<const f32x4 *>(fpa[q] + ST * STAGE);
-                fb[q] = *reinterpret_cast<const f32x4 *>(fpb[q] + ST * STAGE);
-            }
-            __builtin_amdgcn_sched_barrier(0);  // all eight reads in flight before the first MFMA waits (gemm_dma.hip)
-            if (prelu) {  // one uniform branch per k-tile; one v_med3 per element: med3(x, 0, +inf) = max(x, 0) (fmaxf costs two instructions)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) fa[q][e] = __builtin_amdgcn_fmed3f(fa[q][e], 0.f, __builtin_inff());
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][e], fb[q][e], acc[0][0], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);  // the MFMAs stay above the wait for the next tile's DMA
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            tile_multiply(fpa, ST * STAGE, fpb, ST * STAGE, acc[0][0], prelu);
         };
         {
             int kt = kt0;
@@ -231,33 +212,12 @@ __global__ __launch_bounds__(256, 4) void conv3_dma_kernel(const GemmDesc g, con
         }
         if (SPLIT && part) {
             // piece hand-off (gemm_common.hpp); both LDS stages are idle here
-#pragma unroll
-            for (int r = 0; r < 16; ++r) __hip_atomic_store(&part[(wave * 16 + r) * 64 + lane], acc[0][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            split_store_piece(part, wave, lane, acc[0][0]);
             const long long ub = (long long)lt * nkt;
             int g0, g1;
             const bool last = split_handoff(sp, &sp.cnt[lt], ub, nkt, reinterpret_cast<int *>(smem), tid, g0, g1);
             if (last) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
-                const float *base = sp.ws + (wave * 16) * 64 + lane;
-                int gg = g0;
-                for (; gg + 1 <= g1; gg += 2) {
-                    const float *qa = split_piece<SPLIT_SLOT>(base, sp, gg, ub);
-                    const float *qb = split_piece<SPLIT_SLOT>(base, sp, gg + 1, ub);
-                    float ta[16], tb[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        ta[r] = __hip_atomic_load(qa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        tb[r] = __hip_atomic_load(qb + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[0][0][r] = (acc[0][0][r] + ta[r]) + tb[r];
-                }
-                if (gg <= g1) {
-                    const float *qa = split_piece<SPLIT_SLOT>(base, sp, gg, ub);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[0][0][r] += __hip_atomic_load(qa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                acc[0][0] = split_merge_pieces<SPLIT_SLOT>(sp, wave, lane, g0, g1, ub);
                 epilogue();
             }
         } else {
@@ -287,12 +247,9 @@ template <int WGM, int EP>
 int launch_conv_ep(const GemmDesc &d, long long tiles, hipStream_t st) {
     static const bool split_on = env_int("EDV_CONV_SPLIT", 1) != 0;  // 0: plain grid always (A/B runs)
     static const bool buf_off = env_int("EDV_CONV_BUF", 1) == 0;     // 0: flat 64-bit DMA source addresses + zero page as in round 1 (A/B runs)
-    // 32-bit byte offsets must reach every tap of every pixel, with room for the "beyond the end" offset of padding lanes
-    const long long frames = (d.M - 1) / ((long long)d.cOH * d.cOW) + 1;
-    // ... and (the buffer epilogue) every element of C, R1 and R2
-    const long long ld_out = std::max(std::max(d.ldc, d.R1 ? d.ldr1 : 0), d.R2 ? d.ldr2 : 0);
-    const bool buf = !buf_off && frames * d.cH * d.cW * d.cC * 4 < (1ll << 31) - (1 << 20) && (long long)d.N * d.ldw * 4 < (1ll << 32) - (1 << 20) &&
-                     (d.M + 64) * ld_out * 4 < (1ll << 32) - 4096;  // rows up to 63 past M must not wrap the 32-bit scalar offsets (gemm_dma.hip, fits_buffer)
+    // 32-bit byte offsets reach every operand (dma_tile.hpp).  OPEN: 64 rows past M is the 64 x 64 tile's figure; the 128 x 32 tile (WGM = 4) runs
+    // up to 127 past M and should pass 128.  It differs only for an output within 32 KB of 4 GB (33 M pixels at Cout <= 32).
+    const bool buf = !buf_off && conv_inputs_fit(d) && buffer_outputs_fit(d, 64);
     const SplitPolicy &pol = conv_dma_split_policy();
     GemmSplit sp{};
     long long grid;
@@ -328,8 +285,7 @@ std::atomic<int> g_conv_impl{0};
 
 // the operand limits of BUF = true (launch_conv_ep) for a launch without C / R1 / R2, plus the one-float-per-row output
 bool dot_fits_buffer(const GemmDesc &d) {
-    const long long frames = (d.M - 1) / ((long long)d.cOH * d.cOW) + 1;
-    return frames * d.cH * d.cW * d.cC * 4 < (1ll << 31) - (1 << 20) && (long long)d.N * d.ldw * 4 < (1ll << 32) - (1 << 20) && (d.M + 128) * 4 < (1ll << 32) - (1 << 20);
+    return conv_inputs_fit(d) && (d.M + 128) * 4 < (1ll << 32) - (1 << 20);
 }
 
 template <int EP>

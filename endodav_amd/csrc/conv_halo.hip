@@ -2,8 +2,9 @@
 //
 // Second implementation of the LOAD_CONV3 contract of conv_dma.hip, for Cout <= 32 and Cin = 32 or 64: same packed weight [Cout][3][3][Cin], same
 // epilogues (bias, compile-time none / ReLU, gamma, R1 / R2, pre_relu on the A fragments; the fused 1x1 of gemm_common.hpp), and the SAME BITS: the
-// k order (tap, then 32-channel block), the fragment-to-k mapping (chunk 2q + lh, element e -> mfma_f32_32x32x2f32), the zero start of the
-// accumulators and the epilogue arithmetic are conv3_dma_kernel's, so tests/test_conv_halo_gpu.py compares with torch.equal.
+// k order (tap, then 32-channel block), the fragment-to-k mapping (chunk 2q + lh, element e -> mfma_f32_32x32x2f32, the (q, e) order of
+// dma_tile.hpp's tile_multiply), the zero start of the accumulators and the epilogue arithmetic are conv3_dma_kernel's, so
+// tests/test_conv_halo_gpu.py compares with torch.equal.
 //
 // What differs is the A side.  conv3_dma_kernel is an im2col GEMM over 128 consecutive rows of M: per k-tile it fetches the rows' 128-byte runs again,
 // so every input pixel crosses the LDS-DMA path nine times (147 KB per 128x32 tile at Cin = 32, next to 36 KB of weights).  Here a workgroup owns an
@@ -26,12 +27,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm_common.hpp"
+#include "dma_tile.hpp"
 
 namespace edv {
 namespace {
 
-constexpr int HBK = 32;                    // k-tile: one 32-channel block of one tap
+constexpr int HBK = TILE_BK;               // k-tile: one 32-channel block of one tap
 constexpr int TH = 8, TW = 16;             // output patch
 constexpr int ROW_BYTES = 3 * 64 * 16;     // one halo row of one channel block in LDS: three DMA instructions
 constexpr int PIX_BYTES = 9 * 16;          // pixel stride inside a row
@@ -85,23 +86,22 @@ __global__ __launch_bounds__(256, NCB == 1 ? 4 : 2) void conv3_halo_kernel(const
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (__attribute__((address_space(3))) void *)(dst + k * 1024), 16, (unsigned)pat[k], (int)so, 0, 0);
         }
     }
-    // ---- W: k-tile kt = (tap, channel block) is columns 32 kt .. of the packed weight; LDS image and swizzle of conv3_dma_kernel ----
+    // ---- W: k-tile kt = (tap, channel block) is columns 32 kt .. of the packed weight; LDS image and swizzle of conv3_dma_kernel (dma_tile.hpp) ----
     const int srow = lane >> 3, spos = lane & 7;
     unsigned vb;
     {
         const int r = 8 * wave_s + srow;
-        const int c = spos ^ ((r >> 1) & 7);
-        const int n = r < g.N ? r : g.N - 1;
+        const int c = tile_chunk(r, spos);
+        const int n = tile_edge_row(r, g.N);
         vb = (unsigned)((n * g.ldw + c * 4) * 4);
     }
     auto issue_w = [&](int kt, int stg) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (__attribute__((address_space(3))) void *)(sW + stg * WSTAGE + 8 * wave_s * HBK), 16, (unsigned)vb, (int)(kt * HBK * 4),
                                                  0, 0);
     };
-    const int swb = (l31 >> 1) & 7;
     const float *fpb[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) fpb[q] = sW + l31 * HBK + (((2 * q + lh) ^ swb) << 2);
+    for (int q = 0; q < 4; ++q) fpb[q] = tile_frag_ptr(sW, l31, q, lh);
     // the lane's output pixel (patch row 2 w + l31 / 16, column l31 % 16): address of its window's top-left halo pixel, chunk lh
     const char *const a0 = patch + (2 * wave_s) * ROW_BYTES + (l31 >> 4) * ROW_BYTES + (l31 & 15) * PIX_BYTES + lh * 16;
 
@@ -122,13 +122,16 @@ __global__ __launch_bounds__(256, NCB == 1 ? 4 : 2) void conv3_halo_kernel(const
     for (int kt = 0; kt < NKT; ++kt) {
         const int stg = kt & 1, tap = kt / NCB, cb = kt - tap * NCB, dy = tap / 3, dx = tap - 3 * dy;
         if (kt + 1 < NKT) issue_w(kt + 1, stg ^ 1);
+        // tile_multiply of dma_tile.hpp (reads, fence, pre-ReLU, 16 MFMAs, fence, waits, barrier: explained there) with the A fragments from the
+        // patch, written out: called as the shared function, the last k-tile schedules differently and the stored epilogue of Cin = 32 gains 16
+        // v_mov (profiles/dma_tile_refactor_notes.txt)
         f32x4 fa[4], fb[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             fa[q] = *reinterpret_cast<const f32x4 *>(a0 + cb * PLANE_BYTES + dy * ROW_BYTES + dx * PIX_BYTES + q * 32);
             fb[q] = *reinterpret_cast<const f32x4 *>(fpb[q] + stg * WSTAGE);
         }
-        __builtin_amdgcn_sched_barrier(0);  // all eight reads in flight before the first MFMA waits (gemm_dma.hip)
+        __builtin_amdgcn_sched_barrier(0);
         if (prelu) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(256, NCB == 1 ? 4 : 2) void conv3_halo_kernel(const
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][e], fb[q][e], acc, 0, 0, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);  // the MFMAs stay above the wait for the next k-tile's W
+        __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();

@@ -40,7 +40,8 @@ inline bool gemm_plain_forced() {
 // ---- device side of the stream-K split (streamk_plan.hpp has the scheme and the host planner) ------------------------------------------------
 // Used by gemm_dma.hip, conv_dma.hip and gemm_x6.hip.  Their form is what kept every kernel's instruction stream unchanged when they were factored
 // out: GemmSplit travels BY VALUE (through a reference the kernel-argument loads lose their amdgpu.noclobber marking and the merge's addressing
-// changes), and the segment arithmetic, the piece stores and the merge loops stay in each kernel (moving them moved the generated code).
+// changes), the merge RETURNS its accumulators (filled through a reference it changes the k loops' waits or the registers of twelve
+// instantiations), and the segment arithmetic stays in each kernel (moving it moved the generated code).
 // Run cursor: the run a workgroup owns (run j = bid / stride; only workgroups with bid % stride == 0 and j < nsplit own one; -1: none), its first
 // unit, one past its last.
 __device__ __forceinline__ int split_run(const GemmSplit sp, bool split, int bid) {
@@ -82,11 +83,11 @@ __device__ __forceinline__ const float *split_piece(const float *base, const Gem
 // ordering comes from sc1.  tests/test_streamk_fuzz_gpu.py::test_piece_exchange_contract_under_uneven_load is the gate to
 // re-run after a toolchain change; the fenced form to switch to is spelled out there.
 //
-// split_handoff: what follows a workgroup's piece stores for split tile lt (the stores themselves stay with each kernel: they differ in the
-// accumulators a wave holds).  cnt = &sp.cnt[lt], ub = lt * nkt = the tile's first unit.  Returns, to every thread of the workgroup, whether this
-// was the tile's last piece to arrive -- the workgroup then merges runs g0 .. g1 (the runs whose unit ranges intersect [ub, ub + nkt)) with
-// agent-scope loads in run order (split_piece) and applies the epilogue.  s_last: one int of LDS that is idle between the k loop and the next
-// tile's first staging write.
+// split_handoff: what follows a workgroup's piece stores for split tile lt (split_store_piece below for the kernels whose wave holds one 32x32
+// block, gemm_dma.hip and conv_dma.hip; gemm_x6.hip keeps its own stores: a wave of it holds other accumulators).  cnt = &sp.cnt[lt], ub = lt * nkt
+// = the tile's first unit.  Returns, to every thread of the workgroup, whether this was the tile's last piece to arrive -- the workgroup then
+// merges runs g0 .. g1 (the runs whose unit ranges intersect [ub, ub + nkt)) with agent-scope loads in run order (split_piece) and applies the
+// epilogue.  s_last: one int of LDS that is idle between the k loop and the next tile's first staging write.
 __device__ __forceinline__ bool split_handoff(const GemmSplit sp, int *cnt, long long ub, int nkt, int *s_last, int tid, int &g0, int &g1) {
     g0 = (int)(ub / sp.chunk), g1 = (int)((ub + nkt - 1) / sp.chunk);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -102,6 +103,40 @@ __device__ __forceinline__ bool split_handoff(const GemmSplit sp, int *cnt, long
     const bool last = *s_last != 0;
     __syncthreads();  // s_last is read before the next tile's staging may overwrite it
     return last;
+}
+
+// The piece of a wave that holds ONE 32x32 block (gemm_dma.hip, conv_dma.hip), in accumulator order: word (wave * 16 + r) * 64 + lane.
+// split_store_piece is the producer's side, before split_handoff; split_merge_pieces the last arriver's, after it: it returns the sum of the pieces of
+// runs g0 .. g1 in run order whatever the arrival order was, two pieces in flight, (acc + a) + b -- the order is part of the result's bits.
+__device__ __forceinline__ void split_store_piece(float *part, int wave, int lane, const f32x16 &acc) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) __hip_atomic_store(&part[(wave * 16 + r) * 64 + lane], acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <int SLOT>
+__device__ __forceinline__ f32x16 split_merge_pieces(const GemmSplit sp, int wave, int lane, int g0, int g1, long long ub) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float *base = sp.ws + (wave * 16) * 64 + lane;
+    int gg = g0;
+    for (; gg + 1 <= g1; gg += 2) {
+        const float *pa = split_piece<SLOT>(base, sp, gg, ub);
+        const float *pb = split_piece<SLOT>(base, sp, gg + 1, ub);
+        float ta[16], tb[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            ta[r] = __hip_atomic_load(pa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tb[r] = __hip_atomic_load(pb + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = (acc[r] + ta[r]) + tb[r];
+    }
+    if (gg <= g1) {
+        const float *pa = split_piece<SLOT>(base, sp, gg, ub);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] += __hip_atomic_load(pa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return acc;
 }
 
 // XCD-aware, bijective block remap: blocks b and b+8 share an XCD (and its L2); give each XCD a contiguous run of

@@ -6,12 +6,8 @@
 // granule is 1280 B, so five 32 KB blocks do not fit 160 KB -- scratch/ubench/lds_residency.hip).
 // The ablation in scratch/ubench/gemm_ablate.hip priced exactly these staging instructions at ~20 % of the loop.
 //
-// LDS image: unpadded 128-byte rows (the DMA destination is lane-linear), 16-byte chunk c of row r stored at chunk
-// position c ^ ((r >> 1) & 7).  The swizzle is applied to the per-lane SOURCE address and to the fragment read
-// (rule 21 of the CDNA guide); a 16-lane ds_read_b128 group then covers 16 distinct (r & 1, chunk) pairs = all 64 banks.
-// Pipeline: tile k+1 is in flight while tile k is multiplied; each wave waits for its own DMAs with a counted
-// s_waitcnt vmcnt before the raw s_barrier that publishes the stage (a plain __syncthreads() would drain vmcnt to 0
-// anyway here, but the raw form keeps the wait where the data is needed).
+// LDS image (unpadded, swizzled 128-byte rows), the multiply of one k-tile and the two-stage pipeline -- tile k+1 in flight while tile k is
+// multiplied, each wave waiting for its own DMAs before the raw s_barrier that publishes the stage -- are dma_tile.hpp's, shared with conv_dma.hip.
 //
 // Measured (profiles/r01_gemm_tile_sweep.txt), with the full epilogue: T=8 qkv 120 -> 111 us, fc2 162 -> 152 us,
 // T=32 qkv 363 -> 340 us (114 TF/s); end to end +2..3 % on ViT-S/B/L.  On bare 8192x8192x1024 the DMA fill rate per CU
@@ -21,7 +17,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm_common.hpp"
+#include "dma_tile.hpp"
 
 // Timeline hook for scratch/ubench/gemm_trace.hip; expands to nothing in the product build.
 #ifndef EDV_GEMM_STAMP
@@ -31,7 +27,7 @@
 namespace edv {
 namespace {
 
-constexpr int DBK = 32, DBM = 64, DBN = 64;
+constexpr int DBK = TILE_BK, DBM = 64, DBN = 64;
 constexpr int DSTAGE = (DBM + DBN) * DBK;  // floats per stage (16 KB)
 
 // Work split: the persistent grid with a stream-K tail of streamk_plan.hpp (scheme and host planner; the device side is in gemm_common.hpp).
@@ -72,8 +68,6 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
     const int bid = xcd_remap(blockIdx.x, G);
     const int nkt = g.K / DBK;
     const int srow = lane >> 3, spos = lane & 7;
-    const int ra = wm * 32 + l31, rb = wn * 32 + l31;
-    const int swa = (ra >> 1) & 7, swb = (rb >> 1) & 7;
 
     const int tile_l0 = sp.whole_rounds * G;
     const int run = split_run(sp, SPLIT, bid);
@@ -110,11 +104,9 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = 16 * wave + 8 * i + srow;   // row within the tile
-            const int c = spos ^ ((r >> 1) & 7);      // logical chunk that lives at this position
-            long long m = m0 + r;
-            m = m < g.M ? m : g.M - 1;                // rows past the edge read a valid row; their results are never stored
-            int n = n0 + r;
-            n = n < g.N ? n : g.N - 1;
+            const int c = tile_chunk(r, spos);
+            const long long m = tile_edge_row<long long>(m0 + r, g.M);
+            const int n = tile_edge_row(n0 + r, g.N);
             const long long am = BUF == 2 ? m : g.a_map(m);
             ga[i] = g.A + am * g.lda + c * 4;
             gb[i] = g.W + (long long)n * g.ldw + c * 4;
@@ -138,12 +130,11 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
                 }
             }
         };
-        // fragment read addresses in stage 0 (the stage toggle is an immediate offset): logical chunk 2q + lh of rows ra / rb
-        const float *pa[4], *pb[4];
+        const float *pa[4], *pb[4];  // fragment read addresses in stage 0
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            pa[q] = smem + ra * DBK + (((2 * q + lh) ^ swa) << 2);
-            pb[q] = smem + DBM * DBK + rb * DBK + (((2 * q + lh) ^ swb) << 2);
+            pa[q] = tile_frag_ptr(smem, wm * 32 + l31, q, lh);
+            pb[q] = tile_frag_ptr(smem + DBM * DBK, wn * 32 + l31, q, lh);
         }
 
         EpiCols<1> cols;
@@ -178,76 +169,17 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
 
-        // (the barrier that ended the previous run's last k-tile also released both LDS stages)
-        issue(kt0, 0);
-        EDV_GEMM_STAMP(1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        EDV_GEMM_STAMP(2);
-        // one k-tile out of stage ST (compile-time): DMA of the next tile into the other stage, all eight fragment reads, sixteen MFMAs
-        auto ktile = [&](int kt, auto st_tag) {
-            constexpr int ST = decltype(st_tag)::value;
-            if (kt + 1 < kt1) issue(kt + 1, ST ^ 1);  // the other stage was last read in the previous k-tile (barrier passed)
-            f32x4 fa[4], fb[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {  // k = 8q + 4h .. 8q + 4h + 3 (the permuted-k trick of gemm.hip)
-                fa[q] = *reinterpret_cast<const f32x4 *>(pa[q] + ST * DSTAGE);
-                fb[q] = *reinterpret_cast<const f32x4 *>(pb[q] + ST * DSTAGE);
-            }
-            // all eight reads are in flight before the first MFMA waits for its pair (left alone the scheduler sinks each pair of reads
-            // to its four MFMAs and re-uses one register quad: an LDS round trip exposed four times per k-tile)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q][e], fb[q][e], acc[0][0], 0, 0, 0);
-            // this wave's DMAs of tile kt+1 have landed, its fragment reads of tile kt are done -> publish / release.  (The fence keeps the
-            // MFMAs above the wait: they touch registers only, and the scheduler otherwise sinks fifteen of them below the barrier -- the
-            // wave then waits for its DMA one MFMA after issuing it instead of sixteen.)
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        };
-        {
-            int kt = kt0;
-            for (; kt + 1 < kt1; kt += 2) {
-                ktile(kt, std::integral_constant<int, 0>{});
-                ktile(kt + 1, std::integral_constant<int, 1>{});
-            }
-            if (kt < kt1) ktile(kt, std::integral_constant<int, 0>{});
-        }
+        tile_k_loop<DSTAGE>(kt0, kt1, issue, pa, pb, acc[0][0], false, [](int slot) { EDV_GEMM_STAMP(slot); });
         EDV_GEMM_STAMP(3);
         if (SPLIT && part) {
             // piece hand-off (gemm_common.hpp: sc1 stores, every wave's vmcnt(0), barrier, one agent-scope counter add; the last arriver acquires
             // and then reads every piece with sc1 loads in run order); both LDS stages are idle between the k loop and the next tile's first DMA
-#pragma unroll
-            for (int r = 0; r < 16; ++r) __hip_atomic_store(&part[(wave * 16 + r) * 64 + lane], acc[0][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            split_store_piece(part, wave, lane, acc[0][0]);
             const long long ub = (long long)lt * nkt;
             int g0, g1;
             const bool last = split_handoff(sp, &sp.cnt[lt], ub, nkt, reinterpret_cast<int *>(smem), tid, g0, g1);
             if (last) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
-                const float *base = sp.ws + (wave * 16) * 64 + lane;
-                int gg = g0;
-                for (; gg + 1 <= g1; gg += 2) {  // two pieces in flight; summed in run order whatever the arrival order was
-                    const float *pa = split_piece<SLOT>(base, sp, gg, ub);
-                    const float *pb = split_piece<SLOT>(base, sp, gg + 1, ub);
-                    float ta[16], tb[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        ta[r] = __hip_atomic_load(pa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        tb[r] = __hip_atomic_load(pb + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[0][0][r] = (acc[0][0][r] + ta[r]) + tb[r];
-                }
-                if (gg <= g1) {
-                    const float *pa = split_piece<SLOT>(base, sp, gg, ub);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[0][0][r] += __hip_atomic_load(pa + r * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                acc[0][0] = split_merge_pieces<SLOT>(sp, wave, lane, g0, g1, ub);
                 epilogue(m0, n0);
             }
         } else {
@@ -262,13 +194,7 @@ __global__ __launch_bounds__(256, 4) void gemm_dma_kernel(const GemmDesc g, cons
 // operands the 32-bit buffer offsets reach (byte offset of the last element the loop may touch, rows clamped to the edge)
 inline bool fits_buffer(const GemmDesc &d) {
     const long long a_rows = d.a_map(d.M - 1) + 1, lim = (1ll << 32) - (1 << 20);
-    if (!(a_rows * d.lda * 4 < lim && (long long)d.N * d.ldw * 4 < lim)) return false;
-    // The buffer epilogue (identity row maps only: EP 1..3) addresses C, R1 and R2 with 32-bit byte offsets as well, and it masks ragged edges
-    // through the descriptor alone: a tile's rows run up to 63 past M, and their scalar offsets ((row0 + dr) * ld + col0) * 4 are computed in 32
-    // bits -- they must not wrap, or a row past the end would come back INTO range and be stored.  Lanes past column N carry 0xfffff000, which
-    // must lie at or beyond num_records = M * ld * 4.  Both hold iff (M + 64) rows of the widest operand stay below 2^32 - 4096 bytes.
-    const long long ld = std::max(std::max(d.ldc, d.R1 ? d.ldr1 : 0), d.R2 ? d.ldr2 : 0);
-    return (long long)(d.M + 64) * ld * 4 < (1ll << 32) - 4096;
+    return a_rows * d.lda * 4 < lim && (long long)d.N * d.ldw * 4 < lim && buffer_outputs_fit(d, DBM);  // (a tile's rows run up to 63 past M)
 }
 
 template <int STORE, int EP>
