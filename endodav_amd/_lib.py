@@ -165,6 +165,9 @@ SIGNATURES = {
     # the same with the frame's depth scale as a seventh unknown: 37 sums (additive, ABI stays 15)
     "edv_icp_scaled_workspace": (C.c_size_t, [_i32, _i32, _i32]),
     "edv_icp_scaled_sums": (C.c_int, [C.c_void_p, _i64, C.POINTER(_f64), C.POINTER(_f64), _fp, _fp, _i32, _i32, _f64, _fp, _fp, C.c_size_t, C.c_void_p]),
+    # both with a colour block behind the geometric one: the frames and the view's colours (uint8), cols = 6 or 7, 2 * 29 or 2 * 37 sums (additive, ABI stays 15)
+    "edv_icp_colour_workspace": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "edv_icp_colour_sums": (C.c_int, [C.c_void_p, _i64, _fp, C.POINTER(_f64), C.POINTER(_f64), _fp, _fp, _fp, _i32, _i32, _f64, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

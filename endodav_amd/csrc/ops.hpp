@@ -210,6 +210,13 @@ int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const d
 size_t icp_scaled_workspace(int h, int w, int step);
 int icp_scaled_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh,
                     int mw, double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream);
+// the same step (cols = 6) or the scaled one (cols = 7) with a colour block behind the geometric one: per geometric pair the live frame's intensity
+// (frames uint8 [n][h][w][3]) against the model view's colour image (uint8 [mh][mw][3]) sampled bilinearly where the point projects; 2 * 29 or
+// 2 * 37 sums, as many workspace doubles a tile; the geometric block has the bits of icp_sums / icp_scaled_sums
+size_t icp_colour_workspace(int h, int w, int step, int cols);  // 0 also for cols outside {6, 7}
+int icp_colour_sums(const CloudSel &s, long long frame, const uint8_t *frames, const double *live_cam, const double *model_cam, const float *model_depth,
+                    const float *model_normals, const uint8_t *model_colors, int mh, int mw, double max_dist2, int cols, double *sums, void *ws, size_t ws_bytes,
+                    hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -8,12 +8,16 @@
 //   icp_tile   one workgroup per tile of ICP_TILE output pixels of the cloud's grid in row-major order, one thread per pixel: the pixel's 29
 //              terms in fp64 (the upper triangle of J J^T, J e, e e and 1; 29 times +0 for a pixel without a pair), summed over the wave by a
 //              butterfly and over the four waves in wave order (common.hpp's block_sum_store), one row of 29 doubles per tile in the workspace
-//   icp_total  one workgroup: thread j adds value j of the tiles in index order, starting from tile 0's, and stores sums[j]
+//   icp_total  a workgroup of 64 per 64 values (one for 29 or 37): thread j adds value j of the tiles in index order, starting from tile 0's, and stores sums[j]
 // The two cameras travel in the launch arguments, read from host memory before the call returns: the live pose changes with every iteration and
 // nothing is staged.  The model is addressed only after its pixel passed the range test in fp64, and the live frame only inside the grid, so a
 // guess that looks anywhere reads nothing outside the arrays.
 // No atomics, no workgroup waits for another, a fixed order of every addition: the same input gives the same bits on every call.  Every slot of
 // the workspace that is read and all 29 (37) outputs are written on every call.  Contraction is off for the whole file and the division is IEEE's.
+// With colour (icp_colour_sums) every geometric pair also compares the live frame's intensity with the model view's colour image, sampled
+// bilinearly where the point projects: a second block of 29 (37) terms with the intensity's gradient for N and the intensity difference for e.
+//   icp_colour_tile   icp_tile with 2 * 29 (37) terms a pixel: the geometric block through the same icp_terms, so with the same bits, then the colour block
+//   icp_total         as above, two workgroups for the 58 or 74 values
 #include <cmath>
 
 #include "ops.hpp"
@@ -40,13 +44,22 @@ __device__ __forceinline__ void rows3(const double *M, double a, double b, doubl
     for (int i = 0; i < 3; ++i) o[i] = (M[3 * i] * a + M[3 * i + 1] * b) + M[3 * i + 2] * c;
 }
 
-// the 29 (COLS = 6) or 37 (COLS = 7) terms of output pixel q < grid_pixels of the live frame; false, with `a` untouched, for a pixel without a pair
-template <int COLS>
+// what the colour term takes over from a geometric pair: the source pixel of the live frame, the lever arm, the point in the model camera's
+// frame and where it projects
+struct IcpPair {
+    int p;
+    double rho[3], q0, q1, q2, um, vm;
+};
+
+// the T = 29 (COLS = 6) or 37 (COLS = 7) terms of output pixel q < grid_pixels of the live frame into a[0..T); false, with `a` and `g` untouched
+// but for g.p, for a pixel without a pair.  `a` may be longer: the colour kernel keeps its second block behind the first.
+template <int COLS, int LEN>
 __device__ __forceinline__ bool icp_terms(const CloudSel &s, const IcpCams &c, const float *__restrict__ xf, const uint8_t *__restrict__ mf, int ow, unsigned q,
                                           const float *__restrict__ model_depth, const float *__restrict__ model_normals, int mh, int mw, double max_dist2,
-                                          double (&a)[icp_term_count(COLS)]) {
+                                          double (&a)[LEN], IcpPair &g) {
+    static_assert(LEN >= icp_term_count(COLS));
     int ox, oy;
-    const int p = source_pixel(s, ow, q, ox, oy);
+    const int p = g.p = source_pixel(s, ow, q, ox, oy);
     float z;
     if (!kept(s, xf[p], mf ? mf[p] : 1u, z)) return false;
     const double u = ((double)ox + 0.5) * (double)s.step, v = ((double)oy + 0.5) * (double)s.step;
@@ -94,6 +107,54 @@ __device__ __forceinline__ bool icp_terms(const CloudSel &s, const IcpCams &c, c
     for (int j = 0; j < COLS; ++j) a[TRI + j] = J[j] * e;
     a[TRI + COLS] = e * e;
     a[TRI + COLS + 1] = 1.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) g.rho[i] = rho[i];
+    g.q0 = q0, g.q1 = q1, g.q2 = q2, g.um = um, g.vm = vm;
+    return true;
+}
+
+// (0.299*R + 0.587*G) + 0.114*B of a uint8 triple
+__device__ __forceinline__ double intensity(const uint8_t *__restrict__ rgb) { return (0.299 * (double)rgb[0] + 0.587 * (double)rgb[1]) + 0.114 * (double)rgb[2]; }
+
+// the colour block of a pixel that has the geometric pair g: its T terms into a[0..T); false, with `a` untouched, where there is no colour pair
+template <int COLS>
+__device__ __forceinline__ bool icp_colour_terms(const IcpCams &c, const IcpPair &g, const uint8_t *__restrict__ live_rgb, const float *__restrict__ model_depth,
+                                                 const uint8_t *__restrict__ model_colors, int mh, int mw, double *__restrict__ a) {
+    const double gu = g.um - 0.5, gv = g.vm - 0.5;
+    if (!(mw >= 2 && mh >= 2 && gu >= 0.0 && gu <= (double)(mw - 1) && gv >= 0.0 && gv <= (double)(mh - 1))) return false;  // in fp64, before any conversion
+    const int x0 = min((int)gu, mw - 2), y0 = min((int)gv, mh - 2);  // 0 <= x0 <= mw - 2 and 0 <= y0 <= mh - 2: the four pixels lie in the view
+    const double fx = gu - (double)x0, fy = gv - (double)y0;
+    const size_t at = (size_t)y0 * (unsigned)mw + (unsigned)x0;
+    if (!(model_depth[at] > 0.0f && model_depth[at + 1] > 0.0f && model_depth[at + (unsigned)mw] > 0.0f && model_depth[at + (unsigned)mw + 1] > 0.0f)) return false;
+    const double I00 = intensity(model_colors + at * 3), I10 = intensity(model_colors + (at + 1) * 3);
+    const double I01 = intensity(model_colors + (at + (unsigned)mw) * 3), I11 = intensity(model_colors + (at + (unsigned)mw + 1) * 3);
+    const double Yl = intensity(live_rgb + (size_t)g.p * 3);
+    const double top = I00 + fx * (I10 - I00), bot = I01 + fx * (I11 - I01);
+    const double Im = top + fy * (bot - top);
+    const double Iu = (I10 - I00) + fy * ((I11 - I01) - (I10 - I00));
+    const double Iv = (I01 - I00) + fx * ((I11 - I10) - (I01 - I00));
+    // through the projection, into the model camera's frame, then into the world
+    const double *W = c.model + 21, *K = c.model + 33;
+    const double ka = K[0] * g.q0 + K[1] * g.q1, kb = K[3] * g.q0 + K[4] * g.q1;
+    const double gq0 = (Iu * K[0] + Iv * K[3]) / g.q2, gq1 = (Iu * K[1] + Iv * K[4]) / g.q2, gq2 = -((Iu * ka + Iv * kb) / (g.q2 * g.q2));
+    double G[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) G[j] = (W[j] * gq0 + W[4 + j] * gq1) + W[8 + j] * gq2;
+    const double r = Yl - Im;
+    const double *rho = g.rho;
+    double J[COLS] = {rho[1] * G[2] - rho[2] * G[1], rho[2] * G[0] - rho[0] * G[2], rho[0] * G[1] - rho[1] * G[0], G[0], G[1], G[2]};
+    if constexpr (COLS == 7) J[6] = (rho[0] * G[0] + rho[1] * G[1]) + rho[2] * G[2];
+    constexpr int TRI = COLS * (COLS + 1) / 2;
+    int t = 0;
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) {
+#pragma unroll
+        for (int k = j; k < COLS; ++k) a[t++] = J[j] * J[k];
+    }
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) a[TRI + j] = J[j] * r;
+    a[TRI + COLS] = r * r;
+    a[TRI + COLS + 1] = 1.0;
     return true;
 }
 
@@ -109,7 +170,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(CloudSel s, long 
     if (q < grid_pixels) {
         const float *xf = s.x + frame * s.h * s.w;
         const uint8_t *mf = s.mask ? s.mask + frame * s.mask_stride : nullptr;
-        pair = icp_terms<COLS>(s, c, xf, mf, ow, q, model_depth, model_normals, mh, mw, max_dist2, a);
+        IcpPair g;
+        pair = icp_terms<COLS>(s, c, xf, mf, ow, q, model_depth, model_normals, mh, mw, max_dist2, a, g);
     }
     if (!pair) {
 #pragma unroll
@@ -119,9 +181,37 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(CloudSel s, long 
     block_sum_store<TERMS>(a, tile_sums + (size_t)blockIdx.x * TERMS);
 }
 
-// one workgroup: sums[j] = (((t_0 + t_1) + t_2) + ...)[j], tile by tile.  The loads of eight tiles are issued together; the additions keep their order.
+// grid: tiles.  tile_sums [tiles][2 * 29] (COLS = 6) or [tiles][2 * 37] (COLS = 7): the geometric block, then the colour block
+template <int COLS>
+__global__ __launch_bounds__(ICP_THREADS) void icp_colour_tile_kernel(CloudSel s, long long frame, const uint8_t *__restrict__ frames, IcpCams c, int ow, unsigned grid_pixels,
+                                                                      const float *__restrict__ model_depth, const float *__restrict__ model_normals,
+                                                                      const uint8_t *__restrict__ model_colors, int mh, int mw, double max_dist2,
+                                                                      double *__restrict__ tile_sums) {
+    const unsigned q = blockIdx.x * (unsigned)ICP_TILE + threadIdx.x;
+    constexpr int TERMS = icp_term_count(COLS);
+    double a[2 * TERMS];
+    bool pair = false, colour = false;
+    if (q < grid_pixels) {
+        const float *xf = s.x + frame * s.h * s.w;
+        const uint8_t *mf = s.mask ? s.mask + frame * s.mask_stride : nullptr;
+        IcpPair g;
+        pair = icp_terms<COLS>(s, c, xf, mf, ow, q, model_depth, model_normals, mh, mw, max_dist2, a, g);
+        if (pair) colour = icp_colour_terms<COLS>(c, g, frames + (size_t)frame * 3 * s.h * s.w, model_depth, model_colors, mh, mw, a + TERMS);
+    }
+    if (!pair) {
+#pragma unroll
+        for (int j = 0; j < TERMS; ++j) a[j] = 0.0;
+    }
+    if (!colour) {
+#pragma unroll
+        for (int j = TERMS; j < 2 * TERMS; ++j) a[j] = 0.0;
+    }
+    block_sum_store<2 * TERMS>(a, tile_sums + (size_t)blockIdx.x * (2 * TERMS));
+}
+
+// a workgroup per 64 values: sums[j] = (((t_0 + t_1) + t_2) + ...)[j], tile by tile.  The loads of eight tiles are issued together; the additions keep their order.
 __global__ __launch_bounds__(ICP_TOTAL_THREADS) void icp_total_kernel(const double *__restrict__ tile_sums, unsigned tiles, unsigned terms, double *__restrict__ sums) {
-    const unsigned j = threadIdx.x;
+    const unsigned j = blockIdx.x * (unsigned)ICP_TOTAL_THREADS + threadIdx.x;
     if (j >= terms) return;
     double t = tile_sums[j];
     unsigned i = 1;
@@ -159,7 +249,7 @@ template <int COLS>
 int icp_sums_of(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh, int mw,
                 double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
     constexpr int TERMS = icp_term_count(COLS);
-    static_assert(TERMS <= ICP_TOTAL_THREADS, "one thread of the total per term");
+    static_assert(TERMS <= ICP_TOTAL_THREADS, "one workgroup of the total");
     EDV_TRY(check_selection(s));
     EDV_CHECK(frame >= 0 && frame < s.n, "frame outside the clip");
     EDV_CHECK(live_cam && model_cam, "null cameras");
@@ -181,6 +271,34 @@ int icp_sums_of(const CloudSel &s, long long frame, const double *live_cam, cons
     return 0;
 }
 
+template <int COLS>
+int icp_colour_sums_of(const CloudSel &s, long long frame, const uint8_t *frames, const double *live_cam, const double *model_cam, const float *model_depth,
+                       const float *model_normals, const uint8_t *model_colors, int mh, int mw, double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
+    constexpr int TERMS = 2 * icp_term_count(COLS);
+    EDV_TRY(check_selection(s));
+    EDV_CHECK(frame >= 0 && frame < s.n, "frame outside the clip");
+    EDV_CHECK(frames, "null frames");
+    EDV_CHECK(live_cam && model_cam, "null cameras");
+    EDV_CHECK(model_depth && model_normals && aligned_to(model_depth, 4) && aligned_to(model_normals, 4), "model depth or normals missing or not 4-byte aligned");
+    EDV_CHECK(model_colors, "null model colours");
+    EDV_CHECK(mh >= 1 && mw >= 1 && (long long)mh * mw < (1ll << 31), "mh and mw must be at least 1 and the model view below 2^31 pixels");
+    EDV_CHECK(std::isfinite(max_dist2) && max_dist2 >= 0.0, "max_dist2 must be finite and >= 0");
+    EDV_CHECK(sums && aligned_to(sums, 8), "sums missing or not 8-byte aligned");
+    EDV_CHECK(ws && aligned_to(ws, 8) && ws_bytes >= 2 * icp_workspace_of<COLS>(s.h, s.w, s.step),
+              "workspace missing, too small or not 8-byte aligned (edv_icp_colour_workspace)");
+    const IcpGrid g = icp_grid(s.h, s.w, s.step);
+    IcpCams c;
+    for (int i = 0; i < 21; ++i) c.live[i] = live_cam[i];
+    for (int i = 0; i < 39; ++i) c.model[i] = model_cam[i];
+    double *tile_sums = static_cast<double *>(ws);
+    EDV_LAUNCH(icp_colour_tile_kernel<COLS>, dim3(g.tiles), dim3(ICP_THREADS), 0, stream, s, frame, frames, c, g.ow, g.pixels, model_depth, model_normals, model_colors, mh, mw,
+               max_dist2, tile_sums);
+    EDV_LAUNCH_OK();
+    EDV_LAUNCH(icp_total_kernel, dim3((TERMS + ICP_TOTAL_THREADS - 1) / ICP_TOTAL_THREADS), dim3(ICP_TOTAL_THREADS), 0, stream, tile_sums, g.tiles, (unsigned)TERMS, sums);
+    EDV_LAUNCH_OK();
+    return 0;
+}
+
 }  // namespace
 
 int icp_tile_pixels() { return ICP_TILE; }
@@ -196,6 +314,18 @@ int icp_sums(const CloudSel &s, long long frame, const double *live_cam, const d
 int icp_scaled_sums(const CloudSel &s, long long frame, const double *live_cam, const double *model_cam, const float *model_depth, const float *model_normals, int mh,
                     int mw, double max_dist2, double *sums, void *ws, size_t ws_bytes, hipStream_t stream) {
     return icp_sums_of<7>(s, frame, live_cam, model_cam, model_depth, model_normals, mh, mw, max_dist2, sums, ws, ws_bytes, stream);
+}
+
+size_t icp_colour_workspace(int h, int w, int step, int cols) {
+    return cols == 6 ? 2 * icp_workspace_of<6>(h, w, step) : cols == 7 ? 2 * icp_workspace_of<7>(h, w, step) : 0;
+}
+
+int icp_colour_sums(const CloudSel &s, long long frame, const uint8_t *frames, const double *live_cam, const double *model_cam, const float *model_depth,
+                    const float *model_normals, const uint8_t *model_colors, int mh, int mw, double max_dist2, int cols, double *sums, void *ws, size_t ws_bytes,
+                    hipStream_t stream) {
+    EDV_CHECK(cols == 6 || cols == 7, "cols: 6, or 7 with the scale");
+    if (cols == 6) return icp_colour_sums_of<6>(s, frame, frames, live_cam, model_cam, model_depth, model_normals, model_colors, mh, mw, max_dist2, sums, ws, ws_bytes, stream);
+    return icp_colour_sums_of<7>(s, frame, frames, live_cam, model_cam, model_depth, model_normals, model_colors, mh, mw, max_dist2, sums, ws, ws_bytes, stream);
 }
 
 }  // namespace edv

@@ -858,7 +858,9 @@ class endodav(nn.Module):
         ``track`` (a ``fusion.Track``): the video comes without poses.  ``spec`` then holds exactly one pose, the first camera's; every later
         frame is tracked against the volume from the previous frame's pose and integrated where it was found (``fusion.Tsdf.track_clip``), and
         the call returns (the surface, a ``fusion.Tracked`` with the poses found), for every ``surface``.  With ``Track(scale=True)`` every
-        frame's depth scale is tracked with its pose and the frame is integrated at that scale; ``Tracked.scales`` holds the scales found."""
+        frame's depth scale is tracked with its pose and the frame is integrated at that scale; ``Tracked.scales`` holds the scales found.  With
+        ``Track(colour=...)`` every pair also compares the frame's intensity with the coloured volume's (``fusion`` module docstring, "colour"):
+        the frames and the coloured volume are already here, so nothing else changes; it combines with ``scale=True``."""
         from . import cloud, fusion
 
         if surface not in ("points", "mesh", "views"):

@@ -109,7 +109,7 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
                       U @ Vt of its SVD.
             clip      ``track_clip``: the Cloud holds one pose, the first camera's.  Frame 0 is integrated there; each later frame is tracked from
                       the previous frame's pose and integrated at the pose found; a lost frame keeps the previous pose and is not integrated.
-            A scene that is a plane leaves sliding inside the plane unobservable; that is not detected.
+            A scene that is a plane leaves sliding inside the plane unobservable; that is not detected ("colour" below sees it).
             scale     ``Track(scale=True)`` (``edv_icp_scaled_sums``): monocular depth is fixed only up to a scale that wanders from frame to
                       frame, and a tracker that takes every frame in the volume's unit trades that scale for rotation and translation.  With the
                       option the frame's scale is a seventh unknown.  Off (the default), everything above is unchanged to the bit.
@@ -132,6 +132,30 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
                                 carries gain = spec.gain * sigma_{i-1} and the factor starts at 1;  sigma_i = sigma_{i-1} * factor;  it is
                                 integrated with gain = spec.gain * sigma_i at the pose found.  A lost frame keeps the previous pose and scale and
                                 is not integrated.  ``Tracked.scales`` holds sigma_i.
+            colour    ``Track(colour=lambda)`` (``edv_icp_colour_sums``; ``icp_colour_sums`` / ``icp_colour_sums_host``): the sliding that
+                      geometry cannot see is seen by colour.  The volume is coloured, so the model view has a colour image, and the live
+                      frame has its RGB: every geometric pair also compares the two intensities, and a second block of sums holds the normal
+                      equations of that residual.  Off (``None``, the default), everything above is unchanged to the bit.  Needs a coloured
+                      volume and the clip's ``frames``; works with and without ``scale``.
+                      pixel     through the distance test, e and J the rule above, character for character; a pixel without a geometric pair has
+                                no colour pair either.  Then, float64, every operation rounded on its own:
+                                gu = um - 0.5, gv = vm - 0.5;  skip unless mw >= 2, mh >= 2, 0 <= gu <= mw-1 and 0 <= gv <= mh-1;
+                                x0 = min(int(gu), mw-2), y0 = min(int(gv), mh-2);  fx = gu - x0, fy = gv - y0;
+                                skip unless the four model pixels (y0+j, x0+i) all have depth > 0 (a miss's colour is no colour)
+                      intensity Y = (0.299*R + 0.587*G) + 0.114*B of a uint8 triple; I00, I10, I01, I11 of the model's four colours (Iij at
+                                (y0+j, x0+i)), Yl of the live frame at the source pixel the depth was read from
+                      sample    top = I00 + fx*(I10-I00);  bot = I01 + fx*(I11-I01);  Im = top + fy*(bot-top);
+                                Iu = (I10-I00) + fy*((I11-I01) - (I10-I00));  Iv = (I01-I00) + fx*((I11-I10) - (I01-I00)): the patch's exact gradient
+                      gradient  a = K00*q_0 + K01*q_1, b = K10*q_0 + K11*q_1;  gq_0 = (Iu*K00 + Iv*K10) / q_2;  gq_1 = (Iu*K01 + Iv*K11) / q_2;
+                                gq_2 = -((Iu*a + Iv*b) / (q_2*q_2));  in the world g_j = (W[0,j]*gq_0 + W[1,j]*gq_1) + W[2,j]*gq_2
+                      terms     r = Yl - Im; moving P by delta raises the model's intensity by g . delta, so r falls by g . delta, the sign
+                                convention of e and N.  Jc = (rho x g, g), and with ``scale`` Jc_6 = (rho_x*g_x + rho_y*g_y) + rho_z*g_z.  The
+                                geometric block's layout with Jc for J and r for e; +0 throughout where there is no colour pair.
+                      sums      2 T values, T = 29 or 37: [0..T) the geometric block, with the bits ``icp_sums`` gives, [T..2T) the colour block;
+                                the same tiles, butterfly, wave order and tile order.  sums[2T-1] is the number of colour pairs.
+                      solve     A = A_g + lambda^2 * A_c, b = b_g + lambda^2 * b_c, formed on the host in float64, then ``icp_solve`` as above.
+                                lambda weighs one intensity unit (of 255) against one unit of length.  ``pairs``, ``rms``, ``min_pairs`` and the
+                                lost rules stay the geometric block's; no colour pairs adds nothing.
 
 What is not built: hashed or sparse volumes, shading, free-space skipping, and in the tracker an affine correction in disparity (scale and shift;
 the scale alone is ``Track(scale=True)``), image pyramids, compatibility tests between live and model normals, robust weights, loop closure and
@@ -424,8 +448,13 @@ class Track:
     min_weight: float = 1.0                  # of the ray-cast
     scale: bool = False                      # the frame's depth scale is a seventh unknown (module docstring, "scale")
     max_scale_step: float = 0.25             # with ``scale``: a frame whose scale leaves [1/(1+m), 1+m] times its guess is lost
+    colour: float = None                     # lambda, the weight of one intensity unit against one unit of length (module docstring, "colour"); None = geometry alone
 
     def __post_init__(self):
+        if self.colour is not None:
+            if not _positive(self.colour):
+                raise ValueError(f"colour must be None or finite and positive, got {self.colour!r}")
+            object.__setattr__(self, "colour", float(self.colour))
         if not isinstance(self.scale, bool):
             raise ValueError(f"scale must be True or False, got {self.scale!r}")
         if not _positive(self.max_scale_step):
@@ -466,9 +495,9 @@ class Tracked:
     scales: np.ndarray = None                # float64 [n] with ``Track(scale=True)``: sigma_i relative to ``spec.gain``, 1.0 for frame 0; a lost frame repeats the previous one.  None otherwise
 
 
-def _check_icp(depth, spec, model, views, max_dist, frame):
-    """(n, h, w, mask, cams [1 or n, 21], the model's 39 doubles) of checked arguments."""
-    n, h, w = _check_clip(depth, spec, None)
+def _check_icp(depth, spec, model, views, max_dist, frame, frames=None):
+    """(n, h, w, mask, cams [1 or n, 21], the model's 39 doubles) of checked arguments; with ``frames`` the model must carry colours."""
+    n, h, w = _check_clip(depth, spec, frames)
     if not 1 <= n <= MAX_FRAMES or h < 1 or w < 1:
         raise ValueError(f"1 to {MAX_FRAMES} frames that are not empty, got {n} x {h} x {w}")
     if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
@@ -478,6 +507,10 @@ def _check_icp(depth, spec, model, views, max_dist, frame):
     if not isinstance(model, Raycast) or model.normals is None:
         raise ValueError("model must be a fusion.Raycast with normals")
     mh, mw = views.size
+    if frames is not None:
+        a = model.colors
+        if a is None or tuple(a.shape) != (1, mh, mw, 3) or str(a.dtype).replace("torch.", "") != "uint8":
+            raise ValueError(f"expected the model's colors as uint8 {[1, mh, mw, 3]}, got {None if a is None else (a.dtype, tuple(a.shape))}")
     for a, shape, what in ((model.depth, (1, mh, mw), "depth"), (model.normals, (1, mh, mw, 3), "normals")):
         if tuple(a.shape) != shape or str(a.dtype).replace("torch.", "") != "float32":
             raise ValueError(f"expected the model's {what} as float32 {list(shape)}, got {a.dtype} {tuple(a.shape)}")
@@ -517,13 +550,20 @@ def _ordered_sum(terms: np.ndarray) -> np.ndarray:
     return total
 
 
+def _intensity(rgb: np.ndarray) -> np.ndarray:
+    """float64 [...]: (0.299*R + 0.587*G) + 0.114*B of uint8 [..., 3], every operation rounded on its own."""
+    c = rgb.astype(np.float64)
+    return (0.299 * c[..., 0] + 0.587 * c[..., 1]) + 0.114 * c[..., 2]
+
+
 class _IcpHost:
     """One live frame against one model view in numpy: what does not depend on the estimate is formed once."""
     output = "host"
 
-    def __init__(self, depth, spec, model, views, max_dist, frame, scale=False):
+    def __init__(self, depth, spec, model, views, max_dist, frame, scale=False, frames=None):
         depth = np.asarray(depth)
-        n, h, w, mask, cams, self.model_cam = _check_icp(depth, spec, model, views, max_dist, frame)
+        frames = None if frames is None else np.asarray(frames)
+        n, h, w, mask, cams, self.model_cam = _check_icp(depth, spec, model, views, max_dist, frame, frames)
         self.cols = 7 if scale else 6
         self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
         self.max_dist2 = float(max_dist) * float(max_dist)
@@ -538,6 +578,10 @@ class _IcpHost:
         self.u = np.broadcast_to(((np.arange(ow, dtype=np.float64) + 0.5) * float(step))[None, :], (oh, ow)).reshape(-1)
         self.v = np.broadcast_to(((np.arange(oh, dtype=np.float64) + 0.5) * float(step))[:, None], (oh, ow)).reshape(-1)
         self.depth, self.normals = np.asarray(model.depth)[0], np.asarray(model.normals)[0]
+        self.colour = frames is not None
+        if self.colour:                                                  # the intensities of the live grid and of the model view, formed once
+            self.live_y = _intensity(frames[frame][sy][:, sx]).reshape(-1)
+            self.model_y = _intensity(np.asarray(model.colors)[0])
 
     def set_gain(self, gain) -> None:
         """z and kept of the frame again, in float32, for the float32 ``gain``: the cloud's depth rule."""
@@ -556,7 +600,8 @@ class _IcpHost:
         self.z, self.keep = z.astype(np.float64).reshape(-1), keep.reshape(-1)
 
     def terms(self, live: np.ndarray) -> np.ndarray:
-        """float64 [oh * ow, 29 or 37]: the terms of every output pixel for the estimate ``live`` (21 doubles), +0 where there is no pair."""
+        """float64 [oh * ow, 29 or 37]: the terms of every output pixel for the estimate ``live`` (21 doubles), +0 where there is no pair.  With
+        colour twice as many: the colour block behind the geometric one."""
         kinv, rot, pos = live[:9].reshape(3, 3), live[9:18].reshape(3, 3), live[18:]
         m = self.model_cam
         kinv_m, rot_m, pos_m, W, K = m[:9].reshape(3, 3), m[9:18].reshape(3, 3), m[18:21], m[21:33].reshape(3, 4), m[33:].reshape(2, 3)
@@ -588,7 +633,31 @@ class _IcpHost:
                 J.append((rho[0] * N[0] + rho[1] * N[1]) + rho[2] * N[2])
             m = self.cols
             cols = [J[j] * J[k] for j in range(m) for k in range(j, m)] + [J[j] * e for j in range(m)] + [e * e, np.ones_like(e)]
-            return np.stack([np.where(ok, c, 0.0) for c in cols], axis=1)
+            cols = [np.where(ok, c, 0.0) for c in cols]
+            if self.colour:
+                gu, gv = um - 0.5, vm - 0.5
+                ok = ok & (mw >= 2) & (mh >= 2) & (gu >= 0.0) & (gu <= float(mw - 1)) & (gv >= 0.0) & (gv <= float(mh - 1))
+                x0 = np.minimum(np.where(ok, gu, 0.0).astype(np.int64), max(mw - 2, 0))
+                y0 = np.minimum(np.where(ok, gv, 0.0).astype(np.int64), max(mh - 2, 0))
+                x1, y1 = np.minimum(x0 + 1, mw - 1), np.minimum(y0 + 1, mh - 1)      # x0 + 1 and y0 + 1 wherever ok can hold
+                fx, fy = gu - x0.astype(np.float64), gv - y0.astype(np.float64)
+                ok &= (self.depth[y0, x0] > 0) & (self.depth[y0, x1] > 0) & (self.depth[y1, x0] > 0) & (self.depth[y1, x1] > 0)
+                Y = self.model_y
+                I00, I10, I01, I11 = Y[y0, x0], Y[y0, x1], Y[y1, x0], Y[y1, x1]
+                top, bot = I00 + fx * (I10 - I00), I01 + fx * (I11 - I01)
+                Im = top + fy * (bot - top)
+                Iu = (I10 - I00) + fy * ((I11 - I01) - (I10 - I00))
+                Iv = (I01 - I00) + fx * ((I11 - I10) - (I01 - I00))
+                a, b = K[0, 0] * q[0] + K[0, 1] * q[1], K[1, 0] * q[0] + K[1, 1] * q[1]
+                gq = [(Iu * K[0, 0] + Iv * K[1, 0]) / q[2], (Iu * K[0, 1] + Iv * K[1, 1]) / q[2], -((Iu * a + Iv * b) / (q[2] * q[2]))]
+                g = [(W[0, j] * gq[0] + W[1, j] * gq[1]) + W[2, j] * gq[2] for j in range(3)]
+                r = self.live_y - Im
+                J = [rho[1] * g[2] - rho[2] * g[1], rho[2] * g[0] - rho[0] * g[2], rho[0] * g[1] - rho[1] * g[0], g[0], g[1], g[2]]
+                if self.cols == 7:
+                    J.append((rho[0] * g[0] + rho[1] * g[1]) + rho[2] * g[2])
+                more = [J[j] * J[k] for j in range(m) for k in range(j, m)] + [J[j] * r for j in range(m)] + [r * r, np.ones_like(r)]
+                cols += [np.where(ok, c, 0.0) for c in more]
+            return np.stack(cols, axis=1)
 
     def sums(self, live: np.ndarray) -> np.ndarray:
         return _ordered_sum(self.terms(live))
@@ -596,23 +665,30 @@ class _IcpHost:
 
 class _IcpDevice:
     """The same on the GPU (``edv_icp_sums``, or ``edv_icp_scaled_sums`` with ``scale``): the clip, the mask, the model and the workspace are
-    placed once, an estimate costs two launches and one read of 232 (296) bytes, for which the host waits."""
+    placed once, an estimate costs two launches and one read of 232 (296) bytes, for which the host waits.  With ``frames``
+    (``edv_icp_colour_sums``) the frames and the model's colours are placed once too, and the read is of 464 (592) bytes."""
     output = "device"
 
-    def __init__(self, depth, spec, model, views, max_dist, frame, device=None, scale=False):
+    def __init__(self, depth, spec, model, views, max_dist, frame, device=None, scale=False, frames=None):
         if isinstance(depth, torch.Tensor):
             if not depth.is_cuda:
                 raise ValueError("a depth tensor must live on the GPU (pass host data as a numpy array)")
             device = depth.device
         else:
             depth = np.asarray(depth)
-        n, h, w, mask, cams, model_cam = _check_icp(depth, spec, model, views, max_dist, frame)
+        if frames is not None and not isinstance(frames, torch.Tensor):
+            frames = np.asarray(frames)
+        n, h, w, mask, cams, model_cam = _check_icp(depth, spec, model, views, max_dist, frame, frames)
         if device is None:
             device = model.depth.device if isinstance(model.depth, torch.Tensor) and model.depth.is_cuda else torch.device("cuda", torch.cuda.current_device())
         self.device, self.frame, self.lib = device, int(frame), _lib.load()
-        self.name = "edv_icp_scaled_sums" if scale else "edv_icp_sums"
+        self.colour, self.cols = frames is not None, 7 if scale else 6
+        self.name = "edv_icp_colour_sums" if self.colour else "edv_icp_scaled_sums" if scale else "edv_icp_sums"
         self.entry, workspace = getattr(self.lib, self.name), self.lib.edv_icp_scaled_workspace if scale else self.lib.edv_icp_workspace
         count = ICP_SCALED_TERMS if scale else ICP_TERMS
+        if self.colour:
+            count, cols = 2 * count, self.cols
+            workspace = lambda h, w, step: self.lib.edv_icp_colour_workspace(h, w, step, cols)
         self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
         self.max_dist2 = float(max_dist) * float(max_dist)
         self.model_cam = (C.c_double * 39)(*model_cam)
@@ -622,6 +698,8 @@ class _IcpDevice:
             self.mask = None if mask is None else _staged(mask, device)
             self.sel = selection(self.x, spec, self.mask)
             self.depth, self.normals = _on_device(model.depth, device), _on_device(model.normals, device)
+            if self.colour:
+                self.frames, self.colors = _on_device(frames, device), _on_device(model.colors, device)
             self.ws = torch.empty(max(int(workspace(h, w, int(spec.step))), 8), dtype=torch.uint8, device=device)
             self.sums_d = torch.empty(count, dtype=torch.float64, device=device)
             self.sums_h = torch.empty(count, dtype=torch.float64, pin_memory=True)
@@ -633,9 +711,14 @@ class _IcpDevice:
     def sums(self, live: np.ndarray) -> np.ndarray:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            _lib.check(self.entry(C.byref(self.sel), self.frame, (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(), self.normals.data_ptr(),
-                                  self.size[0], self.size[1], self.max_dist2, self.sums_d.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
-                                  C.c_void_p(stream.cuda_stream)), self.name)
+            if self.colour:
+                _lib.check(self.entry(C.byref(self.sel), self.frame, self.frames.data_ptr(), (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(),
+                                      self.normals.data_ptr(), self.colors.data_ptr(), self.size[0], self.size[1], self.max_dist2, self.cols, self.sums_d.data_ptr(),
+                                      self.ws.data_ptr(), self.ws.numel(), C.c_void_p(stream.cuda_stream)), self.name)
+            else:
+                _lib.check(self.entry(C.byref(self.sel), self.frame, (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(), self.normals.data_ptr(),
+                                      self.size[0], self.size[1], self.max_dist2, self.sums_d.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                      C.c_void_p(stream.cuda_stream)), self.name)
             self.sums_h.copy_(self.sums_d, non_blocking=True)
             stream.synchronize()
             return self.sums_h.numpy().copy()
@@ -663,6 +746,35 @@ def icp_sums_host(depth, spec: Cloud, model: Raycast, views: Views, max_dist: fl
     """``icp_sums`` in numpy, the same operations in the same order: the two agree bit for bit."""
     ctx = _IcpHost(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale))
     return ctx.sums(_estimate(ctx, spec, frame))
+
+
+def _check_frames(frames):
+    if frames is None:
+        raise ValueError("the colour sums take the clip's frames, uint8 [n, h, w, 3]")
+    return frames
+
+
+def icp_colour_sums(depth, frames, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0, scale: bool = False) -> np.ndarray:
+    """float64 [2, 29], or [2, 37] with ``scale``: row 0 is ``icp_sums`` of the same arguments, bit for bit, and row 1 the sums of the colour term
+    (module docstring, "colour") over the same pairs: ``frames`` (uint8 [n, h, w, 3], an array or a tensor on the GPU) is the clip's RGB and
+    ``model`` must carry ``colors``.  One tile launch forms both rows.  On the GPU, on the caller's current stream; the host waits for the result."""
+    ctx = _IcpDevice(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale), frames=_check_frames(frames))
+    return ctx.sums(_estimate(ctx, spec, frame)).reshape(2, -1)
+
+
+def icp_colour_sums_host(depth, frames, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0, scale: bool = False) -> np.ndarray:
+    """``icp_colour_sums`` in numpy, the same operations in the same order: the two agree bit for bit."""
+    ctx = _IcpHost(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale), frames=_check_frames(frames))
+    return ctx.sums(_estimate(ctx, spec, frame)).reshape(2, -1)
+
+
+def _with_colour(sums: np.ndarray, weight: float) -> np.ndarray:
+    """The T sums ``icp_solve`` takes from the 2 T of the colour path: A = A_g + weight^2 * A_c and b = b_g + weight^2 * b_c in float64; the last
+    two entries, e e and the count, stay the geometric block's, and so do ``pairs``, ``rms`` and ``min_pairs``."""
+    geometric, colour = sums.reshape(2, -1)
+    out = geometric.copy()
+    out[:-2] = geometric[:-2] + (weight * weight) * colour[:-2]
+    return out
 
 
 def icp_solve(sums, min_pairs):
@@ -697,23 +809,30 @@ def apply_twist(T, xi) -> np.ndarray:
     return T
 
 
-def _track(tsdf, context, depth, spec, track, frame):
+def _track(tsdf, context, depth, spec, track, frame, frames=None):
     """``Tsdf.track`` and ``TsdfHost.track``: everything but the sums is this host code."""
     if not isinstance(track, Track):
         raise ValueError(f"track must be a fusion.Track, got {type(track).__name__}")
     n, h, w = _check_clip(depth, spec, None)
+    if track.colour is None:
+        frames = None                                                    # geometry alone: the frames are not looked at
+    elif not tsdf.coloured or frames is None:
+        raise ValueError("Track(colour=...) compares colours: it takes a coloured volume and the clip's frames")
     if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
         raise ValueError(f"frame must be an integer in 0 .. {n - 1}, got {frame!r}")
     guess = _pose4(spec.pose[frame if spec.pose.shape[0] > 1 else 0])
     views = track.views(spec.K[frame if spec.K.shape[0] > 1 else 0], guess, (h, w))
     model = tsdf.raycast(views, min_weight=track.min_weight, normals=True, output=context.output)
-    ctx = context(depth, spec, model, views, tsdf.volume.trunc if track.max_dist is None else track.max_dist, frame, scale=track.scale)
+    max_dist = tsdf.volume.trunc if track.max_dist is None else track.max_dist
+    ctx = context(depth, spec, model, views, max_dist, frame, scale=track.scale, frames=frames)
     T, pairs, rms, sigma = guess.copy(), 0, float("nan"), 1.0
     lost = (guess, 1.0) if track.scale else (guess,)
     for _ in range(track.iterations):
         if track.scale:
             ctx.set_gain(np.float32(float(spec.gain) * sigma))
         sums = ctx.sums(_live_cam(ctx.kinv, T))
+        if frames is not None:
+            sums = _with_colour(sums, track.colour)
         pairs = int(sums[-1])
         rms = math.sqrt(sums[-2] / sums[-1]) if sums[-1] > 0.0 else float("nan")
         xi = icp_solve(sums, track.min_pairs)
@@ -734,6 +853,8 @@ def _track_clip(tsdf, depth, spec, track, frames):
     if not isinstance(track, Track):
         raise ValueError(f"track must be a fusion.Track, got {type(track).__name__}")
     n, h, w, _, mask = _check_integrate(depth, spec, frames, tsdf.coloured)
+    if track.colour is not None and not tsdf.coloured:
+        raise ValueError("Track(colour=...) compares colours: it takes a coloured volume and the clip's frames")
     if spec.pose.shape[0] != 1:
         raise ValueError(f"tracking starts from one pose, the first camera's; the Cloud holds {spec.pose.shape[0]}")
     out = Tracked(np.zeros((n, 4, 4)), np.zeros(n, np.int64), np.zeros(n), np.zeros(n, bool), np.ones(n) if track.scale else None)
@@ -743,7 +864,7 @@ def _track_clip(tsdf, depth, spec, track, frames):
         if track.scale:
             one = dataclasses.replace(one, gain=float(spec.gain) * sigma)     # the previous frame's scale: the guess
         if i:
-            found, out.pairs[i], out.rms[i], out.lost[i], *factor = tsdf.track(depth[i:i + 1], one, track)
+            found, out.pairs[i], out.rms[i], out.lost[i], *factor = tsdf.track(depth[i:i + 1], one, track, frames=None if frames is None else frames[i:i + 1])
             if not out.lost[i]:
                 T = found
                 one = dataclasses.replace(one, pose=T)
@@ -992,9 +1113,9 @@ class TsdfHost:
                     colors[f, rays] = np.minimum(np.float32(255.0), np.maximum(np.float32(0.0), np.floor(col + np.float32(0.5)))).astype(np.uint8)
         return shaped
 
-    def track(self, depth, spec: Cloud, track: Track, frame: int = 0):
+    def track(self, depth, spec: Cloud, track: Track, frame: int = 0, frames=None):
         """The mirror of ``Tsdf.track``: the same host code around ``icp_sums_host``; a 5-tuple that ends with the scale factor with ``track.scale``."""
-        return _track(self, _IcpHost, np.asarray(depth), spec, track, frame)
+        return _track(self, _IcpHost, np.asarray(depth), spec, track, frame, None if frames is None else np.asarray(frames))
 
     def track_clip(self, depth, spec: Cloud, track: Track, frames=None) -> Tracked:
         """The mirror of ``Tsdf.track_clip``."""
@@ -1161,20 +1282,23 @@ class Tsdf:
             raise ValueError(f"a depth tensor must live on the volume's GPU {self.device} (pass host data as a numpy array)")
         return depth if isinstance(depth, torch.Tensor) else np.asarray(depth)
 
-    def track(self, depth, spec: Cloud, track: Track, frame: int = 0):
+    def track(self, depth, spec: Cloud, track: Track, frame: int = 0, frames=None):
         """The pose of frame ``frame`` of ``depth`` (as for ``integrate``) against this volume (module docstring, "tracking"): the volume ray-cast
         once from the guess, which is ``spec.pose`` with ``spec.K`` and the frame's size, then ``track.iterations`` steps of sums on the GPU, a
         6 x 6 solve on the host and the twist applied.  Returns (T_world_camera float64 [4, 4], pairs, rms, lost); a lost frame returns the
         guess.  With ``track.scale`` the system is 7 x 7 and the tuple ends with the scale factor found, a Python float relative to
-        ``spec.gain``, 1.0 for a lost frame.  On the caller's current stream; the host waits once per step."""
+        ``spec.gain``, 1.0 for a lost frame.  With ``track.colour`` the volume must be coloured and ``frames`` (uint8 [n, h, w, 3], as for
+        ``integrate``) given: every pair also compares the frame's intensity with the model's (module docstring, "colour"); otherwise ``frames``
+        is not looked at.  On the caller's current stream; the host waits once per step."""
         with torch.cuda.device(self.device):
-            return _track(self, _IcpDevice, self._own(depth), spec, track, frame)
+            return _track(self, _IcpDevice, self._own(depth), spec, track, frame, frames)
 
     def track_clip(self, depth, spec: Cloud, track: Track, frames=None) -> Tracked:
         """A clip whose first camera alone is known: ``spec`` holds one pose.  Frame 0 is integrated there; every later frame is tracked from the
         previous frame's pose (with ``track.scale`` also from its scale, and integrated with the scale found: ``Tracked.scales``) and integrated at
         the pose found; a lost frame keeps the previous pose and is not integrated.  ``depth`` and
-        ``frames`` as for ``integrate``, placed on the GPU once."""
+        ``frames`` as for ``integrate``, placed on the GPU once.  With ``track.colour`` frame i is tracked with ``frames[i:i+1]`` too, which takes a
+        coloured volume."""
         with torch.cuda.device(self.device):
             depth = _on_device(self._own(depth), self.device)
             return _track_clip(self, depth, spec, track, None if frames is None else _on_device(frames, self.device))

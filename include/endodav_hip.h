@@ -594,6 +594,48 @@ int edv_icp_scaled_sums(const edv_cloud_selection *sel, int64_t frame, const dou
                         const float *model_normals_dev, int32_t mh, int32_t mw, double max_dist2, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
                         void *stream);
 
+/* ---- the same step with a photometric block (fusion.Track(colour=...), fusion.icp_colour_sums) ----
+ * Additive entry points: the ABI version stays as it is.  Point-to-plane ICP sees nothing of a motion that slides the surface along itself: on
+ * a plane, inside a lumen.  The volume is coloured and so is the live frame; here every geometric pair also compares the live pixel's intensity
+ * with the model view's colour image, sampled bilinearly where the point projects, and a second block of sums holds the normal equations of
+ * that residual.  One launch forms both blocks from one association.  fusion.icp_colour_sums_host is the numpy mirror, bit for bit.
+ * frames_dev: uint8 [n][h][w][3], the clip's RGB frames.  model_colors_dev: uint8 [mh][mw][3], the colours of the same view of
+ *   edv_tsdf_raycast as model_depth_dev and model_normals_dev.  cols: 6 (edv_icp_sums' columns) or 7 (edv_icp_scaled_sums', with J_6);
+ *   T = 29 or 37.
+ * Per kept output pixel everything through the distance test and e, J_0..J_5 (and J_6 with cols = 7) is edv_icp_sums' rule above, character for
+ *   character.  A pixel without a geometric pair has no colour pair either.  A pixel with one continues, in fp64, every operation rounded on
+ *   its own, with um, vm, q_0..q_2, rho, W, K the values that rule formed:
+ *     gu = um - 0.5;  gv = vm - 0.5                                                             (the model's pixel centres lie at the integers)
+ *     no colour pair unless mw >= 2 && mh >= 2 && 0 <= gu && gu <= mw-1 && 0 <= gv && gv <= mh-1, tested in fp64 before any conversion
+ *     x0 = min((int)gu, mw-2);  y0 = min((int)gv, mh-2);  fx = gu - x0;  fy = gv - y0
+ *     no colour pair unless model_depth[y0+j][x0+i] > 0 for i, j in {0, 1}: a miss's colour is (0, 0, 0), which is not a colour
+ *     Y(R, G, B) = (0.299*R + 0.587*G) + 0.114*B of a uint8 triple, the constants the doubles nearest those decimals
+ *     I00, I10, I01, I11 = Y(model_colors[y0][x0]), Y([y0][x0+1]), Y([y0+1][x0]), Y([y0+1][x0+1])
+ *     Yl = Y(frames[frame] at the source pixel the depth was read from): step > 1 samples colour where it samples depth
+ *     top = I00 + fx*(I10-I00);  bot = I01 + fx*(I11-I01);  Im = top + fy*(bot-top)
+ *     Iu = (I10-I00) + fy*((I11-I01) - (I10-I00));  Iv = (I01-I00) + fx*((I11-I10) - (I01-I00))      (the interpolant's exact gradient)
+ *     a = K00*q_0 + K01*q_1;  b = K10*q_0 + K11*q_1
+ *     gq_0 = (Iu*K00 + Iv*K10) / q_2;  gq_1 = (Iu*K01 + Iv*K11) / q_2;  gq_2 = -((Iu*a + Iv*b) / (q_2*q_2))   (in the model camera's frame)
+ *     g_j = (W[0][j]*gq_0 + W[1][j]*gq_1) + W[2][j]*gq_2,  j = 0..2                                            (in the world)
+ *     r = Yl - Im.  Moving P by delta raises the model's intensity by g . delta, so r falls by g . delta: the sign convention of e and N.
+ *     Jc = (rho x g, g), each product rounded and then the difference, exactly as for N;  with cols = 7, Jc_6 = (rho_x*g_x + rho_y*g_y) + rho_z*g_z
+ *   The pixel's colour terms: the layout of the geometric block with Jc for J and r for e: the upper triangle row-major, Jc_j*r, r*r, 1.0.  A
+ *   pixel without a colour pair contributes T times +0.0 to the colour block.
+ * The sums: 2*T values, [0..T) the geometric block and [T..2T) the colour block; exactly as above, tiles of 256 output pixels, a butterfly per
+ *   wave, ((w0 + w1) + w2) + w3 to the workspace as [tile][2*T], then per value the tiles in index order from tile 0's value into
+ *   sums_dev[0..2T); fp64, no atomics.  The geometric block has the bits of edv_icp_sums (cols = 6) or edv_icp_scaled_sums (cols = 7) for the
+ *   same inputs.  sums_dev[2T-1] is the number of colour pairs.  Every workspace slot that is read and all 2*T outputs are written on every call.
+ * On the host (fusion._track) with the weight lambda = Track.colour, an intensity unit against a unit of length: A = A_g + lambda^2 * A_c,
+ *   b = b_g + lambda^2 * b_c, formed in fp64 and solved as before; pairs, rms and the lost rules stay the geometric block's.
+ * The model's colour image is addressed only after the fp64 range tests (0 <= x0 <= mw-2, 0 <= y0 <= mh-2) and the live image only inside its
+ *   grid: a guess that looks anywhere reads nothing outside the arrays.
+ * edv_icp_colour_workspace: 2*T * 8 bytes per tile; 0 for a shape the call refuses or cols outside {6, 7}.  edv_icp_colour_sums: the refusals
+ *   of edv_icp_sums, and also null frames_dev, null model_colors_dev and cols outside {6, 7}; a refused call launches nothing. */
+size_t edv_icp_colour_workspace(int32_t h, int32_t w, int32_t step, int32_t cols);
+int edv_icp_colour_sums(const edv_cloud_selection *sel, int64_t frame, const uint8_t *frames_dev, const double *live_cam_host, const double *model_cam_host,
+                        const float *model_depth_dev, const float *model_normals_dev, const uint8_t *model_colors_dev, int32_t mh, int32_t mw, double max_dist2,
+                        int32_t cols, double *sums_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
