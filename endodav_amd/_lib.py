@@ -168,6 +168,12 @@ SIGNATURES = {
     # both with a colour block behind the geometric one: the frames and the view's colours (uint8), cols = 6 or 7, 2 * 29 or 2 * 37 sums (additive, ABI stays 15)
     "edv_icp_colour_workspace": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "edv_icp_colour_sums": (C.c_int, [C.c_void_p, _i64, _fp, C.POINTER(_f64), C.POINTER(_f64), _fp, _fp, _fp, _i32, _i32, _f64, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
+    # robust tracking (additive, ABI stays 15): the live frame's normal map for frames first .. first + count - 1 (cams on the device, stride 0 or 21), and any
+    # of the sums above with a normal test (live normals, min_cos) and Huber weights (huber, huber_colour); frames and colours may be NULL: no colour block
+    "edv_frame_normals": (C.c_int, [C.c_void_p, _fp, _i32, _i64, _i64, _fp, C.c_void_p]),
+    "edv_icp_robust_workspace": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
+    "edv_icp_robust_sums": (C.c_int, [C.c_void_p, _i64, _fp, C.POINTER(_f64), C.POINTER(_f64), _fp, _fp, _fp, _i32, _i32, _f64, _i32, _fp, _f64, _f64, _f64, _fp, _fp,
+                                      C.c_size_t, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

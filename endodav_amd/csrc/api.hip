@@ -380,6 +380,19 @@ int edv_icp_colour_sums(const edv_cloud_selection *sel, int64_t frame, const uin
     return icp_colour_sums(cloud_sel(*sel), frame, frames_dev, live_cam_host, model_cam_host, model_depth_dev, model_normals_dev, model_colors_dev, mh, mw, max_dist2,
                            cols, sums_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
+int edv_frame_normals(const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, int64_t first, int64_t count, float *normals_dev, void *stream) {
+    EDV_CHECK(sel, "null selection");
+    return frame_normals(cloud_sel(*sel), cams_dev, cam_stride, first, count, normals_dev, (hipStream_t)stream);
+}
+size_t edv_icp_robust_workspace(int32_t h, int32_t w, int32_t step, int32_t cols, int32_t colour) { return icp_robust_workspace(h, w, step, cols, colour); }
+int edv_icp_robust_sums(const edv_cloud_selection *sel, int64_t frame, const uint8_t *frames_dev, const double *live_cam_host, const double *model_cam_host,
+                        const float *model_depth_dev, const float *model_normals_dev, const uint8_t *model_colors_dev, int32_t mh, int32_t mw, double max_dist2,
+                        int32_t cols, const float *live_normals_dev, double min_cos, double huber, double huber_colour, double *sums_dev, void *workspace_dev,
+                        size_t workspace_bytes, void *stream) {
+    EDV_CHECK(sel, "null selection");
+    return icp_robust_sums(cloud_sel(*sel), frame, frames_dev, live_cam_host, model_cam_host, model_depth_dev, model_normals_dev, model_colors_dev, mh, mw, max_dist2,
+                           cols, live_normals_dev, min_cos, huber, huber_colour, sums_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
 
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,

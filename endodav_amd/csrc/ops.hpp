@@ -217,6 +217,17 @@ size_t icp_colour_workspace(int h, int w, int step, int cols);  // 0 also for co
 int icp_colour_sums(const CloudSel &s, long long frame, const uint8_t *frames, const double *live_cam, const double *model_cam, const float *model_depth,
                     const float *model_normals, const uint8_t *model_colors, int mh, int mw, double max_dist2, int cols, double *sums, void *ws, size_t ws_bytes,
                     hipStream_t stream);
+// the live frame's own normals for the tracker's compatibility test: per output pixel of frames first .. first + count - 1 the unit normal in the
+// camera's frame from central differences of the cloud's vertices (Kinv of cams, device doubles [1 or n][21]), (0, 0, 0) where the pixel or one
+// of its four neighbours is not kept or lies outside the grid; normals [count][oh][ow][3], every element written
+int frame_normals(const CloudSel &s, const double *cams, int cam_stride, long long first, long long count, float *normals, hipStream_t stream);
+// any of the steps above (cols = 6 or 7; the colour block exactly when frames and model_colors are both given) with a normal test behind the
+// distance test (live_normals [oh][ow][3] of the frame with min_cos; null: none) and Huber weights on the rows (+inf: none); the layout of the sums
+// stays, and with every option off so do their bits
+size_t icp_robust_workspace(int h, int w, int step, int cols, int colour);  // 0 also for cols outside {6, 7} or colour outside {0, 1}
+int icp_robust_sums(const CloudSel &s, long long frame, const uint8_t *frames, const double *live_cam, const double *model_cam, const float *model_depth,
+                    const float *model_normals, const uint8_t *model_colors, int mh, int mw, double max_dist2, int cols, const float *live_normals, double min_cos, double huber,
+                    double huber_colour, double *sums, void *ws, size_t ws_bytes, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

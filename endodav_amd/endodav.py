@@ -860,7 +860,9 @@ class endodav(nn.Module):
         the call returns (the surface, a ``fusion.Tracked`` with the poses found), for every ``surface``.  With ``Track(scale=True)`` every
         frame's depth scale is tracked with its pose and the frame is integrated at that scale; ``Tracked.scales`` holds the scales found.  With
         ``Track(colour=...)`` every pair also compares the frame's intensity with the coloured volume's (``fusion`` module docstring, "colour"):
-        the frames and the coloured volume are already here, so nothing else changes; it combines with ``scale=True``."""
+        the frames and the coloured volume are already here, so nothing else changes; it combines with ``scale=True``.  With
+        ``Track(min_cos=..., huber=..., huber_colour=...)`` pairs whose normals disagree are dropped and large residuals weighed down
+        (``fusion`` module docstring, "robust"); it combines with both."""
         from . import cloud, fusion
 
         if surface not in ("points", "mesh", "views"):

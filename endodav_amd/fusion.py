@@ -156,10 +156,36 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
                       solve     A = A_g + lambda^2 * A_c, b = b_g + lambda^2 * b_c, formed on the host in float64, then ``icp_solve`` as above.
                                 lambda weighs one intensity unit (of 255) against one unit of length.  ``pairs``, ``rms``, ``min_pairs`` and the
                                 lost rules stay the geometric block's; no colour pairs adds nothing.
+            robust    ``Track(min_cos=..., huber=..., huber_colour=...)`` (``edv_frame_normals``, ``edv_icp_robust_sums``; ``frame_normals`` /
+                      ``frame_normals_host``, ``icp_robust_sums`` / ``icp_robust_sums_host``): the steps above believe every pair that passes the
+                      distance test, and a highlight, an instrument or tissue that moved gives pairs that pass it.  A pair is tested against the
+                      model twice more: by orientation, the live frame's own normal against the model's, and by the size of its residual, a Huber
+                      weight.  All three off (``None``, the default), everything above is unchanged to the bit and the kernels above run; works
+                      with and without ``scale`` and ``colour``.  float64, every operation rounded on its own.
+                      normals   the live frame's normal map on the cloud's output grid, in the camera's frame, so it does not depend on the pose:
+                                vertex   V_i = l_i * float64(z) with u, v, l as in "pixel" above, z (float32) and kept the cloud's
+                                valid    1 <= ox <= ow-2, 1 <= oy <= oh-2, and the pixel and its neighbours (oy, ox-1), (oy, ox+1), (oy-1, ox), (oy+1, ox) kept
+                                normal   a = V(oy, ox+1) - V(oy, ox-1);  b = V(oy+1, ox) - V(oy-1, ox);  c = b x a, each product rounded, then the
+                                         difference: with x right, y down and z forward it points towards the camera, the free side, as the
+                                         model's normals do;  s = (c_0*c_0 + c_1*c_1) + c_2*c_2;  len = sqrt(s);  n_i = float32(c_i / len) if len > 0
+                                A pixel that is not valid or has len = 0 gets (0, 0, 0).  One thread a pixel and frame; the tracker forms the map of
+                                its own frame once, before the first iteration, with the gain of the guess.  With ``scale`` it is not formed again
+                                when the gain changes: a uniform scale does not turn a normal, only the kept set at the near and far edge can differ.
+                      test      after the distance test, when ``min_cos`` is given:  nl = float64(map[oy, ox]);  skip unless (nl_0*nl_0 + nl_1*nl_1) + nl_2*nl_2 > 0;
+                                nw_i = (R[i,0]*nl_0 + R[i,1]*nl_1) + R[i,2]*nl_2 with R of the current estimate;  skip unless
+                                (N_0*nw_0 + N_1*nw_1) + N_2*nw_2 >= min_cos.  A skipped pixel has no pair and no colour pair.
+                      weight    w = 1.0 if |e| <= huber, otherwise huber / |e|;  Jw_j = w * J_j;  the terms are Jw_j*J_k, Jw_j*e, then e*e
+                                unweighted and 1: ``pairs`` and ``rms`` keep their meaning, the layout stays 29 / 37 and ``icp_solve`` is unchanged.
+                                Since 1.0 * x == x, a pair inside the threshold contributes the bits of the plain kernel.  The colour block
+                                likewise with r, ``huber_colour`` and Jc; r*r stays unweighted.  A threshold that is not given is +inf: w = 1.
+                      sums      exactly as above: the same tiles, butterfly, wave order and tile order; no atomics.
+                      Measured on the mirror (tests/test_track_robust_cpu.py): a block of 12.5 % of the live frame 0.04 nearer ends 2.37e-2 rad /
+                      1.40e-2 from the truth with the plain tracker and 5.5e-3 / 3.8e-3 with huber = 0.005; the block replaced by a tilted plane
+                      8.5e-3 / 3.1e-3 against 1.3e-3 / 6.8e-4 with min_cos = 0.985.
 
 What is not built: hashed or sparse volumes, shading, free-space skipping, and in the tracker an affine correction in disparity (scale and shift;
-the scale alone is ``Track(scale=True)``), image pyramids, compatibility tests between live and model normals, robust weights, loop closure and
-relocalisation after a lost frame."""
+the scale alone is ``Track(scale=True)``), image pyramids, a depth-jump test inside the live normals, loop closure and relocalisation after a lost
+frame."""
 from __future__ import annotations
 
 import ctypes as C
@@ -449,12 +475,27 @@ class Track:
     scale: bool = False                      # the frame's depth scale is a seventh unknown (module docstring, "scale")
     max_scale_step: float = 0.25             # with ``scale``: a frame whose scale leaves [1/(1+m), 1+m] times its guess is lost
     colour: float = None                     # lambda, the weight of one intensity unit against one unit of length (module docstring, "colour"); None = geometry alone
+    min_cos: float = None                    # pairs whose live normal, turned by the estimate, has a cosine below this with the model's are dropped (module docstring, "robust"); None = no test
+    huber: float = None                      # the Huber threshold of the point-to-plane residual, a length; None = plain least squares
+    huber_colour: float = None               # the same for the intensity residual, in levels of 255; needs ``colour``
 
     def __post_init__(self):
         if self.colour is not None:
             if not _positive(self.colour):
                 raise ValueError(f"colour must be None or finite and positive, got {self.colour!r}")
             object.__setattr__(self, "colour", float(self.colour))
+        if self.min_cos is not None:
+            if not _number(self.min_cos) or not -1.0 <= self.min_cos <= 1.0:
+                raise ValueError(f"min_cos must be None or a number in [-1, 1], got {self.min_cos!r}")
+            object.__setattr__(self, "min_cos", float(self.min_cos))
+        for name in ("huber", "huber_colour"):
+            x = getattr(self, name)
+            if x is not None:
+                if not _positive(x):
+                    raise ValueError(f"{name} must be None or finite and positive, got {x!r}")
+                object.__setattr__(self, name, float(x))
+        if self.huber_colour is not None and self.colour is None:
+            raise ValueError("huber_colour weighs the colour residual: it needs colour")
         if not isinstance(self.scale, bool):
             raise ValueError(f"scale must be True or False, got {self.scale!r}")
         if not _positive(self.max_scale_step):
@@ -483,6 +524,10 @@ class Track:
     def views(self, K, pose, size) -> Views:
         """The one view the model is cast from."""
         return Views(K, pose, size=size, near=self.near, far=self.far, step=self.step)
+
+    def robust(self) -> dict:
+        """The options of the robust sums that are set; empty: the plain kernels."""
+        return {k: v for k, v in (("min_cos", self.min_cos), ("huber", self.huber), ("huber_colour", self.huber_colour)) if v is not None}
 
 
 @dataclass(eq=False)
@@ -556,25 +601,141 @@ def _intensity(rgb: np.ndarray) -> np.ndarray:
     return (0.299 * c[..., 0] + 0.587 * c[..., 1]) + 0.114 * c[..., 2]
 
 
+def _depth_rule(x: np.ndarray, source: str, scalars, gain):
+    """(z float32, kept) of float32 ``x`` for the float32 ``gain``: the cloud's depth rule with the ``Cloud.scalars()`` given."""
+    lo, span, _, near, far = scalars
+    gain = np.float32(gain)
+    with np.errstate(all="ignore"):
+        if source == "depth":
+            z = x * gain
+        else:
+            scaled = lo + span * x
+            z = np.float32(1.0) / scaled
+            z = z * gain
+        keep = (z > near) & (z < far)
+    return z, keep
+
+
+def _grid_samples(h: int, w: int, step: int):
+    """The source rows and columns of the cloud's output grid."""
+    oh, ow = -(-h // step), -(-w // step)
+    return np.minimum(np.arange(oh, dtype=np.int64) * step + step // 2, h - 1), np.minimum(np.arange(ow, dtype=np.int64) * step + step // 2, w - 1)
+
+
+def _grid_normals(z: np.ndarray, keep: np.ndarray, kinv: np.ndarray, step: int) -> np.ndarray:
+    """float32 [oh, ow, 3]: the live normals (module docstring, "robust") of one frame's output grid from its z (float32) and kept."""
+    oh, ow = z.shape
+    out = np.zeros((oh, ow, 3), np.float32)
+    if oh < 3 or ow < 3:
+        return out
+    u = ((np.arange(ow, dtype=np.float64) + 0.5) * float(step))[None, :]
+    v = ((np.arange(oh, dtype=np.float64) + 0.5) * float(step))[:, None]
+    with np.errstate(all="ignore"):
+        zz = z.astype(np.float64)
+        V = [((kinv[i, 0] * u + kinv[i, 1] * v) + kinv[i, 2]) * zz for i in range(3)]
+        a = [V[i][1:-1, 2:] - V[i][1:-1, :-2] for i in range(3)]
+        b = [V[i][2:, 1:-1] - V[i][:-2, 1:-1] for i in range(3)]
+        c = [b[1] * a[2] - b[2] * a[1], b[2] * a[0] - b[0] * a[2], b[0] * a[1] - b[1] * a[0]]
+        length = np.sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2])
+        valid = keep[1:-1, 1:-1] & keep[1:-1, 2:] & keep[1:-1, :-2] & keep[2:, 1:-1] & keep[:-2, 1:-1] & (length > 0.0)
+        for i in range(3):
+            out[1:-1, 1:-1, i] = np.where(valid, c[i] / length, 0.0).astype(np.float32)
+    return out
+
+
+def _check_normals(depth, spec):
+    n, h, w = _check_clip(depth, spec, None)
+    if not 1 <= n <= MAX_FRAMES or h < 1 or w < 1:
+        raise ValueError(f"1 to {MAX_FRAMES} frames that are not empty, got {n} x {h} x {w}")
+    return n, h, w, spec.frame_mask(n, h, w), spec.cams(n)
+
+
+def frame_normals_host(depth, spec: Cloud) -> np.ndarray:
+    """``frame_normals`` in numpy, the same operations in the same order: the two agree bit for bit."""
+    depth = np.asarray(depth)
+    n, h, w, mask, cams = _check_normals(depth, spec)
+    step = int(spec.step)
+    sy, sx = _grid_samples(h, w, step)
+    scalars = spec.scalars()
+    out = np.empty((n, sy.shape[0], sx.shape[0], 3), np.float32)
+    for f in range(n):
+        z, keep = _depth_rule(depth[f][sy][:, sx], spec.source, scalars, scalars[2])
+        if mask is not None:
+            keep &= (mask[f] if mask.ndim == 3 else mask)[sy][:, sx] != 0
+        out[f] = _grid_normals(z, keep, cams[f if cams.shape[0] > 1 else 0, :9].reshape(3, 3), step)
+    return out
+
+
+def _frame_normals_device(lib, sel, cams_d: torch.Tensor, first: int, count: int, device) -> torch.Tensor:
+    """``edv_frame_normals`` of frames first .. first + count - 1 of the selection ``sel`` on the current stream: float32 [count, oh, ow, 3] on the GPU."""
+    step = int(sel.step)
+    out = torch.empty((count, -(-int(sel.h) // step), -(-int(sel.w) // step), 3), dtype=torch.float32, device=device)
+    _lib.check(lib.edv_frame_normals(C.byref(sel), cams_d.data_ptr(), 21 if cams_d.shape[0] > 1 else 0, first, count, out.data_ptr(),
+                                     C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "edv_frame_normals")
+    return out
+
+
+def frame_normals(depth, spec: Cloud, output: str = "host"):
+    """float32 [n, oh, ow, 3]: the normal of every pixel of the cloud's output grid in its camera's frame (module docstring, "robust"), from central
+    differences of the clip's own vertices; (0, 0, 0) where the pixel or one of its four neighbours is not kept, and on the grid's border.
+    ``depth`` is float32 [n, h, w], a numpy array or a tensor on the GPU; the pose of ``spec`` is not looked at.  On the GPU, on the caller's
+    current stream: a numpy array, complete when returned, or with ``output="device"`` a tensor ordered on that stream."""
+    if output not in ("host", "device"):
+        raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+    if isinstance(depth, torch.Tensor):
+        if not depth.is_cuda:
+            raise ValueError("a depth tensor must live on the GPU (pass host data as a numpy array)")
+        device = depth.device
+    else:
+        depth, device = np.asarray(depth), torch.device("cuda", torch.cuda.current_device())
+    n, h, w, mask, cams = _check_normals(depth, spec)
+    with torch.cuda.device(device):
+        x = _on_device(depth, device)
+        mask_d = None if mask is None else _staged(mask, device)
+        out = _frame_normals_device(_lib.load(), selection(x, spec, mask_d), _staged(cams, device), 0, n, device)
+        if output == "device":
+            return out
+        host = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()
+        return host.numpy().copy()
+
+
+def _check_robust(colour: bool, min_cos=None, huber=None, huber_colour=None):
+    """(min_cos or None, huber, huber_colour) of checked options of the robust sums; a threshold that is not given is +inf."""
+    if min_cos is not None and (not _number(min_cos) or not -1.0 <= min_cos <= 1.0):
+        raise ValueError(f"min_cos must be None or a number in [-1, 1], got {min_cos!r}")
+    for name, x in (("huber", huber), ("huber_colour", huber_colour)):
+        if x is not None and (isinstance(x, bool) or not isinstance(x, (int, float, np.floating, np.integer)) or not x > 0.0):
+            raise ValueError(f"{name} must be None or positive (inf: no weight), got {x!r}")
+    if huber_colour is not None and not colour:
+        raise ValueError("huber_colour weighs the colour residual: it needs the frames and a model with colours")
+    return None if min_cos is None else float(min_cos), math.inf if huber is None else float(huber), math.inf if huber_colour is None else float(huber_colour)
+
+
 class _IcpHost:
-    """One live frame against one model view in numpy: what does not depend on the estimate is formed once."""
+    """One live frame against one model view in numpy: what does not depend on the estimate is formed once.  ``robust``: None for the plain sums, or
+    the options of ``_check_robust`` by name (all of them optional) for the robust ones; the live normals are then formed here, once."""
     output = "host"
 
-    def __init__(self, depth, spec, model, views, max_dist, frame, scale=False, frames=None):
+    def __init__(self, depth, spec, model, views, max_dist, frame, scale=False, frames=None, robust=None):
         depth = np.asarray(depth)
         frames = None if frames is None else np.asarray(frames)
         n, h, w, mask, cams, self.model_cam = _check_icp(depth, spec, model, views, max_dist, frame, frames)
+        self.robust = None if robust is None else _check_robust(frames is not None, **robust)
         self.cols = 7 if scale else 6
         self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
         self.max_dist2 = float(max_dist) * float(max_dist)
         step = int(spec.step)
-        oh, ow = -(-h // step), -(-w // step)
-        sy = np.minimum(np.arange(oh, dtype=np.int64) * step + step // 2, h - 1)
-        sx = np.minimum(np.arange(ow, dtype=np.int64) * step + step // 2, w - 1)
+        sy, sx = _grid_samples(h, w, step)
+        oh, ow = sy.shape[0], sx.shape[0]
         self.source, self.scalars = spec.source, spec.scalars()
         self.x = depth[frame][sy][:, sx]
         self.unmasked = None if mask is None else (mask[frame] if mask.ndim == 3 else mask)[sy][:, sx] != 0
         self.set_gain(self.scalars[2])
+        self.live_normals = None
+        if self.robust is not None and self.robust[0] is not None:         # with the gain of the spec, and not again when ``set_gain`` changes it
+            self.live_normals = _grid_normals(self.z32, self.keep.reshape(oh, ow), self.kinv.reshape(3, 3), step).astype(np.float64).reshape(-1, 3)
         self.u = np.broadcast_to(((np.arange(ow, dtype=np.float64) + 0.5) * float(step))[None, :], (oh, ow)).reshape(-1)
         self.v = np.broadcast_to(((np.arange(oh, dtype=np.float64) + 0.5) * float(step))[:, None], (oh, ow)).reshape(-1)
         self.depth, self.normals = np.asarray(model.depth)[0], np.asarray(model.normals)[0]
@@ -585,19 +746,10 @@ class _IcpHost:
 
     def set_gain(self, gain) -> None:
         """z and kept of the frame again, in float32, for the float32 ``gain``: the cloud's depth rule."""
-        lo, span, _, near, far = self.scalars
-        gain, x = np.float32(gain), self.x
-        with np.errstate(all="ignore"):
-            if self.source == "depth":
-                z = x * gain
-            else:
-                scaled = lo + span * x
-                z = np.float32(1.0) / scaled
-                z = z * gain
-            keep = (z > near) & (z < far)
+        self.z32, keep = _depth_rule(self.x, self.source, self.scalars, gain)
         if self.unmasked is not None:
             keep &= self.unmasked
-        self.z, self.keep = z.astype(np.float64).reshape(-1), keep.reshape(-1)
+        self.z, self.keep = self.z32.astype(np.float64).reshape(-1), keep.reshape(-1)
 
     def terms(self, live: np.ndarray) -> np.ndarray:
         """float64 [oh * ow, 29 or 37]: the terms of every output pixel for the estimate ``live`` (21 doubles), +0 where there is no pair.  With
@@ -632,7 +784,17 @@ class _IcpHost:
             if self.cols == 7:
                 J.append((rho[0] * N[0] + rho[1] * N[1]) + rho[2] * N[2])
             m = self.cols
-            cols = [J[j] * J[k] for j in range(m) for k in range(j, m)] + [J[j] * e for j in range(m)] + [e * e, np.ones_like(e)]
+            Jw = J
+            if self.robust is not None:
+                min_cos, huber, huber_colour = self.robust
+                if self.live_normals is not None:
+                    nl = [self.live_normals[:, i] for i in range(3)]
+                    has = (nl[0] * nl[0] + nl[1] * nl[1]) + nl[2] * nl[2] > 0.0
+                    nw = [(rot[i, 0] * nl[0] + rot[i, 1] * nl[1]) + rot[i, 2] * nl[2] for i in range(3)]
+                    ok &= has & ((N[0] * nw[0] + N[1] * nw[1]) + N[2] * nw[2] >= min_cos)
+                weight = np.where(np.abs(e) <= huber, 1.0, huber / np.abs(e))
+                Jw = [weight * j for j in J]
+            cols = [Jw[j] * J[k] for j in range(m) for k in range(j, m)] + [Jw[j] * e for j in range(m)] + [e * e, np.ones_like(e)]
             cols = [np.where(ok, c, 0.0) for c in cols]
             if self.colour:
                 gu, gv = um - 0.5, vm - 0.5
@@ -655,7 +817,11 @@ class _IcpHost:
                 J = [rho[1] * g[2] - rho[2] * g[1], rho[2] * g[0] - rho[0] * g[2], rho[0] * g[1] - rho[1] * g[0], g[0], g[1], g[2]]
                 if self.cols == 7:
                     J.append((rho[0] * g[0] + rho[1] * g[1]) + rho[2] * g[2])
-                more = [J[j] * J[k] for j in range(m) for k in range(j, m)] + [J[j] * r for j in range(m)] + [r * r, np.ones_like(r)]
+                Jw = J
+                if self.robust is not None:
+                    weight = np.where(np.abs(r) <= huber_colour, 1.0, huber_colour / np.abs(r))
+                    Jw = [weight * j for j in J]
+                more = [Jw[j] * J[k] for j in range(m) for k in range(j, m)] + [Jw[j] * r for j in range(m)] + [r * r, np.ones_like(r)]
                 cols += [np.where(ok, c, 0.0) for c in more]
             return np.stack(cols, axis=1)
 
@@ -666,10 +832,11 @@ class _IcpHost:
 class _IcpDevice:
     """The same on the GPU (``edv_icp_sums``, or ``edv_icp_scaled_sums`` with ``scale``): the clip, the mask, the model and the workspace are
     placed once, an estimate costs two launches and one read of 232 (296) bytes, for which the host waits.  With ``frames``
-    (``edv_icp_colour_sums``) the frames and the model's colours are placed once too, and the read is of 464 (592) bytes."""
+    (``edv_icp_colour_sums``) the frames and the model's colours are placed once too, and the read is of 464 (592) bytes.  With ``robust`` (as for
+    ``_IcpHost``; ``edv_icp_robust_sums``) the frame's normal map is formed once too (``edv_frame_normals``, one more launch) and stays on the GPU."""
     output = "device"
 
-    def __init__(self, depth, spec, model, views, max_dist, frame, device=None, scale=False, frames=None):
+    def __init__(self, depth, spec, model, views, max_dist, frame, device=None, scale=False, frames=None, robust=None):
         if isinstance(depth, torch.Tensor):
             if not depth.is_cuda:
                 raise ValueError("a depth tensor must live on the GPU (pass host data as a numpy array)")
@@ -689,6 +856,11 @@ class _IcpDevice:
         if self.colour:
             count, cols = 2 * count, self.cols
             workspace = lambda h, w, step: self.lib.edv_icp_colour_workspace(h, w, step, cols)
+        self.robust = None if robust is None else _check_robust(self.colour, **robust)
+        if self.robust is not None:                                      # ``edv_icp_robust_sums``: one entry for all four, the same launches and reads
+            self.name, cols, colour = "edv_icp_robust_sums", self.cols, int(self.colour)
+            self.entry = self.lib.edv_icp_robust_sums
+            workspace = lambda h, w, step: self.lib.edv_icp_robust_workspace(h, w, step, cols, colour)
         self.kinv = cams[frame if cams.shape[0] > 1 else 0, :9]
         self.max_dist2 = float(max_dist) * float(max_dist)
         self.model_cam = (C.c_double * 39)(*model_cam)
@@ -700,6 +872,9 @@ class _IcpDevice:
             self.depth, self.normals = _on_device(model.depth, device), _on_device(model.normals, device)
             if self.colour:
                 self.frames, self.colors = _on_device(frames, device), _on_device(model.colors, device)
+            self.live_normals = None
+            if self.robust is not None and self.robust[0] is not None:   # the frame's own normals, once, with the gain of the spec
+                self.live_normals = _frame_normals_device(self.lib, self.sel, _staged(cams, device), self.frame, 1, device)
             self.ws = torch.empty(max(int(workspace(h, w, int(spec.step))), 8), dtype=torch.uint8, device=device)
             self.sums_d = torch.empty(count, dtype=torch.float64, device=device)
             self.sums_h = torch.empty(count, dtype=torch.float64, pin_memory=True)
@@ -711,7 +886,13 @@ class _IcpDevice:
     def sums(self, live: np.ndarray) -> np.ndarray:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            if self.colour:
+            if self.robust is not None:
+                min_cos, huber, huber_colour = self.robust
+                _lib.check(self.entry(C.byref(self.sel), self.frame, self.frames.data_ptr() if self.colour else None, (C.c_double * 21)(*live), self.model_cam,
+                                      self.depth.data_ptr(), self.normals.data_ptr(), self.colors.data_ptr() if self.colour else None, self.size[0], self.size[1],
+                                      self.max_dist2, self.cols, _lib.ptr(self.live_normals), -1.0 if min_cos is None else min_cos, huber, huber_colour,
+                                      self.sums_d.data_ptr(), self.ws.data_ptr(), self.ws.numel(), C.c_void_p(stream.cuda_stream)), self.name)
+            elif self.colour:
                 _lib.check(self.entry(C.byref(self.sel), self.frame, self.frames.data_ptr(), (C.c_double * 21)(*live), self.model_cam, self.depth.data_ptr(),
                                       self.normals.data_ptr(), self.colors.data_ptr(), self.size[0], self.size[1], self.max_dist2, self.cols, self.sums_d.data_ptr(),
                                       self.ws.data_ptr(), self.ws.numel(), C.c_void_p(stream.cuda_stream)), self.name)
@@ -766,6 +947,26 @@ def icp_colour_sums_host(depth, frames, spec: Cloud, model: Raycast, views: View
     """``icp_colour_sums`` in numpy, the same operations in the same order: the two agree bit for bit."""
     ctx = _IcpHost(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale), frames=_check_frames(frames))
     return ctx.sums(_estimate(ctx, spec, frame)).reshape(2, -1)
+
+
+def icp_robust_sums(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0, scale: bool = False, frames=None, min_cos: float = None,
+                    huber: float = None, huber_colour: float = None) -> np.ndarray:
+    """``icp_sums`` (float64 [29] or [37]) or, with ``frames`` and a model that carries ``colors``, ``icp_colour_sums`` ([2, 29] or [2, 37]) under the
+    robust rule (module docstring, "robust"; ``edv_icp_robust_sums``).  ``min_cos``: the frame's own normals are formed (``frame_normals`` of that
+    frame, with the gain of ``spec``) and a pair is kept only where they agree with the model's to that cosine; None: no test.  ``huber`` and
+    ``huber_colour``: the Huber thresholds of the two residuals, positive; None or inf: no weight.  With all three off the sums have the bits of
+    ``icp_sums`` or ``icp_colour_sums``.  On the GPU, on the caller's current stream; the host waits for the result."""
+    ctx = _IcpDevice(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale), frames=frames, robust=dict(min_cos=min_cos, huber=huber, huber_colour=huber_colour))
+    sums = ctx.sums(_estimate(ctx, spec, frame))
+    return sums if frames is None else sums.reshape(2, -1)
+
+
+def icp_robust_sums_host(depth, spec: Cloud, model: Raycast, views: Views, max_dist: float, frame: int = 0, scale: bool = False, frames=None, min_cos: float = None,
+                         huber: float = None, huber_colour: float = None) -> np.ndarray:
+    """``icp_robust_sums`` in numpy, the same operations in the same order: the two agree bit for bit."""
+    ctx = _IcpHost(depth, spec, model, views, max_dist, frame, scale=_check_scale(scale), frames=frames, robust=dict(min_cos=min_cos, huber=huber, huber_colour=huber_colour))
+    sums = ctx.sums(_estimate(ctx, spec, frame))
+    return sums if frames is None else sums.reshape(2, -1)
 
 
 def _with_colour(sums: np.ndarray, weight: float) -> np.ndarray:
@@ -824,7 +1025,7 @@ def _track(tsdf, context, depth, spec, track, frame, frames=None):
     views = track.views(spec.K[frame if spec.K.shape[0] > 1 else 0], guess, (h, w))
     model = tsdf.raycast(views, min_weight=track.min_weight, normals=True, output=context.output)
     max_dist = tsdf.volume.trunc if track.max_dist is None else track.max_dist
-    ctx = context(depth, spec, model, views, max_dist, frame, scale=track.scale, frames=frames)
+    ctx = context(depth, spec, model, views, max_dist, frame, scale=track.scale, frames=frames, robust=track.robust() or None)   # the live normals: once, here
     T, pairs, rms, sigma = guess.copy(), 0, float("nan"), 1.0
     lost = (guess, 1.0) if track.scale else (guess,)
     for _ in range(track.iterations):

@@ -636,6 +636,52 @@ int edv_icp_colour_sums(const edv_cloud_selection *sel, int64_t frame, const uin
                         const float *model_depth_dev, const float *model_normals_dev, const uint8_t *model_colors_dev, int32_t mh, int32_t mw, double max_dist2,
                         int32_t cols, double *sums_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- robust tracking: live normal maps, a normal test and Huber weights (fusion.Track(min_cos=..., huber=..., huber_colour=...)) ----
+ * Additive entry points: the ABI version stays as it is.  The steps above believe every pair that passes the distance test; a highlight, an
+ * instrument or tissue that moved gives pairs that pass it and are wrong.  Two tests of a pair against the model: its orientation (the live
+ * frame's own normal against the model's) and the size of its residual (a Huber weight).  fusion.frame_normals_host and
+ * fusion.icp_robust_sums_host are the numpy mirrors, bit for bit.  All of it fp64, every operation rounded on its own.
+ *
+ * edv_frame_normals: the normal of every output pixel of frames first .. first + count - 1 of the selection, in the CAMERA's frame (it does not
+ *   depend on the pose), into normals_dev [count][oh][ow][3] fp32 on the cloud's output grid.  cams_dev and cam_stride are edv_cloud_scatter's
+ *   (device doubles, 21 a camera, stride 0 or 21); only Kinv is read.  One thread per output pixel and frame; every element is written once.
+ *     vertex  of output pixel (oy, ox), with z (fp32) and kept the selection's:  u = (ox + 0.5) * step;  v = (oy + 0.5) * step;
+ *             l_i = (Kinv[i][0]*u + Kinv[i][1]*v) + Kinv[i][2];  V_i = l_i * (double)z
+ *     valid   when 1 <= ox <= ow-2 and 1 <= oy <= oh-2 and the pixel and its four neighbours (oy, ox-1), (oy, ox+1), (oy-1, ox), (oy+1, ox) are kept
+ *     normal  a = V(oy, ox+1) - V(oy, ox-1);  b = V(oy+1, ox) - V(oy-1, ox);  c = b x a, each product rounded and then the difference:
+ *             c_0 = b_1*a_2 - b_2*a_1, c_1 = b_2*a_0 - b_0*a_2, c_2 = b_0*a_1 - b_1*a_0.  With x right, y down and z forward c points towards
+ *             the camera, the free side, as the model's normals do.  s = (c_0*c_0 + c_1*c_1) + c_2*c_2;  len = sqrt(s), correctly rounded;
+ *             n_i = (float)(c_i / len) if len > 0 (NaN fails)
+ *     A pixel that is not valid or has len = 0 gets (0, 0, 0).
+ *   Null pointers, a selection the cloud refuses, cameras not 8-byte or normals not 4-byte aligned, a cam_stride other than 0 and 21, first < 0,
+ *   count < 1 and first + count > sel->n return non-zero and launch nothing.
+ *
+ * edv_icp_robust_sums: edv_icp_sums (cols = 6) or edv_icp_scaled_sums (cols = 7), and with the colour block edv_icp_colour_sums, with the two
+ *   tests.  The colour block is present exactly when frames_dev and model_colors_dev are both given; T = 29 or 37, and the sums are T or 2*T.
+ *   live_normals_dev: [oh][ow][3] fp32, edv_frame_normals of frame `frame` alone (first = frame, count = 1); null: no normal test.
+ *   huber, huber_colour: the thresholds of the geometric and of the colour residual, > 0; +inf turns a weight off.
+ * Per kept output pixel q everything through the distance test, e and J is edv_icp_sums' rule above, character for character.  Then:
+ *     normal test, when live_normals_dev is given:  nl = (double)live_normals[q][0..2];  skip unless (nl_0*nl_0 + nl_1*nl_1) + nl_2*nl_2 > 0;
+ *             nw_i = (R[i][0]*nl_0 + R[i][1]*nl_1) + R[i][2]*nl_2 with R of the current estimate;  cos = (N_0*nw_0 + N_1*nw_1) + N_2*nw_2;
+ *             skip unless cos >= min_cos.  A skipped pixel has no pair and no colour pair.
+ *     weight  w = 1.0 if |e| <= huber, otherwise huber / |e| (IEEE division)
+ *     terms   Jw_j = w * J_j;  Jw_j*J_k for j <= k in the order above;  Jw_j*e;  then e*e, UNWEIGHTED, and 1.0: the number of pairs and their rms
+ *             keep their meaning and the layout stays 29 / 37.  Since 1.0 * x == x, a pair inside the threshold contributes the plain kernel's bits.
+ *     colour  the colour pair by edv_icp_colour_sums' rule; w_c from |r| and huber_colour;  Jcw_j = w_c * Jc_j;  Jcw_j*Jc_k, Jcw_j*r, r*r, 1.0
+ * The sums exactly as above: tiles of 256, the butterfly, ((w0 + w1) + w2) + w3 to the workspace, the tiles in index order; no atomics; every
+ *   workspace slot that is read and every output is written on every call.  With no normals and both thresholds +inf the sums have the bits of
+ *   edv_icp_sums, edv_icp_scaled_sums or edv_icp_colour_sums.
+ * edv_icp_robust_workspace: T * 8 bytes per tile, twice that with colour = 1; 0 for a shape the call refuses, cols outside {6, 7} or colour
+ *   outside {0, 1}.  edv_icp_robust_sums: the refusals of edv_icp_sums, and also cols outside {6, 7}, a min_cos that is not finite or outside
+ *   [-1, 1] (with or without live normals), a threshold that is NaN or not > 0, and live normals not 4-byte aligned; a refused call launches
+ *   nothing. */
+int edv_frame_normals(const edv_cloud_selection *sel, const double *cams_dev, int32_t cam_stride, int64_t first, int64_t count, float *normals_dev, void *stream);
+size_t edv_icp_robust_workspace(int32_t h, int32_t w, int32_t step, int32_t cols, int32_t colour);
+int edv_icp_robust_sums(const edv_cloud_selection *sel, int64_t frame, const uint8_t *frames_dev, const double *live_cam_host, const double *model_cam_host,
+                        const float *model_depth_dev, const float *model_normals_dev, const uint8_t *model_colors_dev, int32_t mh, int32_t mw, double max_dist2,
+                        int32_t cols, const float *live_normals_dev, double min_cos, double huber, double huber_colour, double *sums_dev, void *workspace_dev,
+                        size_t workspace_bytes, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
