@@ -4,7 +4,7 @@ ARCH     ?= gfx950
 CSRC     := endodav_amd/csrc
 OUT      := endodav_amd/lib/libendodav_hip.so
 SRCS     := $(CSRC)/gemm.hip $(CSRC)/gemm_dma.hip $(CSRC)/gemm_x6.hip $(CSRC)/conv_dma.hip $(CSRC)/conv_halo.hip $(CSRC)/attn_spatial.hip $(CSRC)/attn_spatial_bwd.hip $(CSRC)/norms.hip $(CSRC)/temporal.hip \
-            $(CSRC)/resample.hip $(CSRC)/stitch.hip $(CSRC)/metrics.hip $(CSRC)/render.hip $(CSRC)/pointcloud.hip $(CSRC)/tsdf.hip $(CSRC)/tsdf_mesh.hip $(CSRC)/tsdf_raycast.hip $(CSRC)/tsdf_track.hip $(CSRC)/prep.hip $(CSRC)/bwd.hip $(CSRC)/wgrad.hip $(CSRC)/bias_colsum.hip $(CSRC)/loss.hip $(CSRC)/loss_trainer.hip $(CSRC)/engine.hip $(CSRC)/engine_prepare.hip $(CSRC)/engine_forward.hip $(CSRC)/engine_backward.hip $(CSRC)/api.hip
+            $(CSRC)/resample.hip $(CSRC)/stitch.hip $(CSRC)/metrics.hip $(CSRC)/render.hip $(CSRC)/pointcloud.hip $(CSRC)/tsdf.hip $(CSRC)/tsdf_mesh.hip $(CSRC)/tsdf_raycast.hip $(CSRC)/tsdf_track.hip $(CSRC)/tsdf_pyramid.hip $(CSRC)/prep.hip $(CSRC)/bwd.hip $(CSRC)/wgrad.hip $(CSRC)/bias_colsum.hip $(CSRC)/loss.hip $(CSRC)/loss_trainer.hip $(CSRC)/engine.hip $(CSRC)/engine_prepare.hip $(CSRC)/engine_forward.hip $(CSRC)/engine_backward.hip $(CSRC)/api.hip
 OBJS     := $(SRCS:$(CSRC)/%.hip=build/%.o)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -Wall -Wno-unused-function -fno-gpu-rdc
 

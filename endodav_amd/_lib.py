@@ -174,6 +174,12 @@ SIGNATURES = {
     "edv_icp_robust_workspace": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "edv_icp_robust_sums": (C.c_int, [C.c_void_p, _i64, _fp, C.POINTER(_f64), C.POINTER(_f64), _fp, _fp, _fp, _i32, _i32, _f64, _i32, _fp, _f64, _f64, _f64, _fp, _fp,
                                       C.c_size_t, C.c_void_p]),
+    # coarse-to-fine tracking (additive, ABI stays 15): levels 1 .. L of one frame in one launch, float32 depth through a CloudSelection or uint8 RGB; the
+    # levels lie one behind the other at the pixel offsets edv_pyramid_pixels states (host int64 [L])
+    "edv_pyramid_max_levels": (_i32, []),
+    "edv_pyramid_pixels": (C.c_size_t, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "edv_depth_pyramid": (C.c_int, [C.c_void_p, _i64, _i32, _f32, _fp, C.c_void_p]),
+    "edv_rgb_pyramid": (C.c_int, [_fp, _i64, _i32, _i32, _i64, _i32, _fp, C.c_void_p]),
     "edv_stitch_workspace": (C.c_size_t, []),
     "edv_stitch_fit": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, C.c_size_t, C.c_void_p]),
     "edv_stitch_apply": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, C.c_void_p]),

@@ -393,6 +393,17 @@ int edv_icp_robust_sums(const edv_cloud_selection *sel, int64_t frame, const uin
     return icp_robust_sums(cloud_sel(*sel), frame, frames_dev, live_cam_host, model_cam_host, model_depth_dev, model_normals_dev, model_colors_dev, mh, mw, max_dist2,
                            cols, live_normals_dev, min_cos, huber, huber_colour, sums_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
+int32_t edv_pyramid_max_levels(void) { return pyramid_max_levels(); }
+size_t edv_pyramid_pixels(int32_t h, int32_t w, int32_t levels, int64_t *offsets_host) {
+    return pyramid_pixels(h, w, levels, reinterpret_cast<long long *>(offsets_host));
+}
+int edv_depth_pyramid(const edv_cloud_selection *sel, int64_t frame, int32_t levels, float one_plus_jump, float *levels_dev, void *stream) {
+    EDV_CHECK(sel, "null selection");
+    return depth_pyramid(cloud_sel(*sel), frame, levels, one_plus_jump, levels_dev, (hipStream_t)stream);
+}
+int edv_rgb_pyramid(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, int64_t frame, int32_t levels, uint8_t *levels_dev, void *stream) {
+    return rgb_pyramid(frames_dev, n, h, w, frame, levels, levels_dev, (hipStream_t)stream);
+}
 
 size_t edv_stitch_workspace(void) { return stitch_workspace(); }
 int edv_stitch_fit(const float *disp_dev, int32_t ih, int32_t iw, const float *tail_dev, int32_t fh, int32_t fw, float *st_dev, void *workspace_dev,

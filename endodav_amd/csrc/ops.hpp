@@ -228,6 +228,14 @@ size_t icp_robust_workspace(int h, int w, int step, int cols, int colour);  // 0
 int icp_robust_sums(const CloudSel &s, long long frame, const uint8_t *frames, const double *live_cam, const double *model_cam, const float *model_depth,
                     const float *model_normals, const uint8_t *model_colors, int mh, int mw, double max_dist2, int cols, const float *live_normals, double min_cos, double huber,
                     double huber_colour, double *sums, void *ws, size_t ws_bytes, hipStream_t stream);
+// coarse-to-fine tracking (tsdf_pyramid.hip): levels 1 .. `levels` of one frame in one launch, level l + 1 half the size of level l (an odd last
+// row or column dropped), the levels one behind the other in `out`.  depth: the raw depth of the selection (step 1, near_z >= 0, gain > 0; the
+// depth rule without the gain) where the cloud keeps the pixel; per 2 x 2 block the mean of the valid values within one_plus_jump of the
+// smallest, +0 where none is valid.  rgb: per channel (a + b + c + d + 2) >> 2
+int pyramid_max_levels();  // level 0 included
+size_t pyramid_pixels(int h, int w, int levels, long long *offsets);  // the pixels of levels 1 .. levels together and, where not null, offsets[l - 1] = the pixels in front of level l; 0 for a shape the calls refuse
+int depth_pyramid(const CloudSel &s, long long frame, int levels, float one_plus_jump, float *out, hipStream_t stream);
+int rgb_pyramid(const uint8_t *frames, long long n, int h, int w, long long frame, int levels, uint8_t *out, hipStream_t stream);
 // pos-embed bicubic resample (vision_transformer.py:186-217): grid [S,S,D] -> [oh,ow,D]
 int bicubic_pos(const float *grid, float *out, int S, int D, int oh, int ow, float scale_h, float scale_w, hipStream_t st);
 

@@ -182,10 +182,50 @@ its depth rule, mask and cameras are a ``cloud.Cloud`` with ``step = 1``:
                       Measured on the mirror (tests/test_track_robust_cpu.py): a block of 12.5 % of the live frame 0.04 nearer ends 2.37e-2 rad /
                       1.40e-2 from the truth with the plain tracker and 5.5e-3 / 3.8e-3 with huber = 0.005; the block replaced by a tilted plane
                       8.5e-3 / 3.1e-3 against 1.3e-3 / 6.8e-4 with min_cos = 0.985.
+            pyramid   ``Track(pyramid=(i_0, ..., i_L), jump=...)`` (``edv_depth_pyramid``, ``edv_rgb_pyramid``; ``depth_pyramid`` / ``depth_pyramid_host``,
+                      ``rgb_pyramid`` / ``rgb_pyramid_host``): coarse to fine.  Every step above runs on the live frame's full grid against a model
+                      cast at full size.  A step at half size works on a quarter of the pixels and rays, and with large pixels the same motion is
+                      a small displacement, which is what projective association needs.  ``pyramid`` lists the steps per level, finest first;
+                      ``None`` (the default): everything above is unchanged to the bit and the same kernels run.
+                      levels    level 0 is the cloud's grid of the live frame; it needs ``step == 1``, float32(near) >= 0 and gain > 0.  Level l+1
+                                has size (h_l // 2, w_l // 2): an odd last row or column is dropped.  Every level must hold a pixel; at most
+                                ``PYRAMID_MAX_LEVELS`` levels in all (the library's constant: the kernel's tile of level 0 is 2^(that - 1) pixels a
+                                side).  K_l = diag(2^-l, 2^-l, 1) K, exactly: a power of two, and pixel centres at x + 0.5 make u_l = u_0 / 2^l.
+                      raw depth float32 d_0 = x for ``source="depth"`` and 1 / (lo + span * x) for ``"disparity"``: the cloud's rule without its last
+                                multiply by the gain.  A pixel of level 0 is valid when the cloud keeps it: the mask, and near < z < far with
+                                z = d_0 * gain32 at the gain of the guess.  A pixel of a level >= 1 is valid when its stored value is not 0.
+                      reduce    float32, every operation rounded on its own.  The block (2y, 2x), (2y, 2x+1), (2y+1, 2x), (2y+1, 2x+1) of level l, in
+                                that order:  m = the smallest valid value;  a valid value is used when d <= m * one_plus_jump, with
+                                one_plus_jump = float32(1.0 + jump) formed in Python doubles and rounded once;  s = the used values added in block
+                                order, starting from the first used one;  c = their count;  the stored value is s / float32(c), or +0 where nothing
+                                is valid.  The nearest surface wins, so a block across a depth edge is not smeared; this is also the first
+                                depth-jump test the live side gets.  ``jump = inf`` uses every valid value, ``jump = 0`` only those equal to m.
+                      colour    RGB level l+1 is per channel (a + b + c + d + 2) >> 2 over the same block, in integers; validity is ignored, as the
+                                frames carry none.
+                      consuming a level l >= 1 is an ordinary clip for the kernels above: Cloud(K=K_l, pose=T, source="depth", gain=the gain of
+                                level 0, near, far, mask=None, step=1) over the stored level, so z = d_l * gain32 and the near/far test drops the
+                                zeros.  The gain was kept out of the stored values, so ``set_gain`` of "scale" works unchanged.
+                      track     the levels run from L down to 0; with ``pyramid`` set ``iterations`` is not used.  A level with 0 steps is skipped
+                                entirely: no ray-cast, no normals.  The two pyramids are formed once per tracked frame, up to the coarsest level
+                                that is run.  Entering level l the model is ``raycast(track.views(K_l, T, (h_l, w_l)))`` from the current estimate T
+                                (the guess for the first level run).  ``max_dist``, ``min_pairs``, ``min_cos``, ``huber``, ``huber_colour``, ``colour``
+                                and the scale's update and bounds apply at every level as they are (a wider ``max_dist`` on coarse levels was tried
+                                on the mirror and lost accuracy); the live normals for ``min_cos`` are formed once per level on the level's
+                                selection, with the gain of the guess.  A level that loses the frame loses the frame: the guess comes back.
+                                ``pairs`` and ``rms`` are those of the last step run;  R is re-orthonormalised once, after the last level.
+                      One launch a frame makes all depth levels and one all colour levels (a workgroup per 32 x 32 tile of level 0, which holds
+                      whole blocks of every level; levels 2 and up are reduced through LDS); no atomics, every pixel of every level written once.
+                      Measured on the mirror (tests/test_track_pyramid_cpu.py) on the scene of tests/track_cases.py, guess the identity,
+                      min_pairs = 16: at five times the scene's motion (0.195 rad) the plain tracker with 19 steps ends 6.83e-1 rad / 4.99e-1
+                      from the truth, ``pyramid=(10, 5, 4)`` 9.2e-4 / 5.5e-4; at the scene's own motion 9.4e-4 / 4.5e-4 against 7.1e-5 / 1.3e-5.
+                      On so small and smooth a scene the gain in reach is modest (4.5 times converges either way, 5.5 times is lost either way,
+                      the overlap runs out).  Times on the GPU at 518 x 518 are in DESIGN.md, "Coarse-to-fine tracking": there the coarse plans
+                      are slower than six full-size steps, because a ray-cast is bound by the length of a ray and a step by its launches and
+                      its host wait, so the option is for reach, not for speed.
 
 What is not built: hashed or sparse volumes, shading, free-space skipping, and in the tracker an affine correction in disparity (scale and shift;
-the scale alone is ``Track(scale=True)``), image pyramids, a depth-jump test inside the live normals, loop closure and relocalisation after a lost
-frame."""
+the scale alone is ``Track(scale=True)``), a depth-jump test inside the live normals (the pyramid's ``jump`` tests the blocks it averages, level 0
+has none), a model pyramid down-sampled instead of re-cast, a solve on the device, loop closure and relocalisation after a lost frame."""
 from __future__ import annotations
 
 import ctypes as C
@@ -204,6 +244,8 @@ from .cloud import MAX_FRAMES, Cloud, PointCloud, _check_clip, _on_device, selec
 def __getattr__(name):
     if name == "TILE_VOXELS":  # voxels per workgroup of the extraction kernels, from the library's own constant
         return int(_lib.load().edv_tsdf_tile_voxels())
+    if name == "PYRAMID_MAX_LEVELS":  # the levels of a pyramid, level 0 included: the pyramid kernel's tile is 2^(levels - 1) pixels a side
+        return int(_lib.load().edv_pyramid_max_levels())
     raise AttributeError(name)
 
 
@@ -478,8 +520,19 @@ class Track:
     min_cos: float = None                    # pairs whose live normal, turned by the estimate, has a cosine below this with the model's are dropped (module docstring, "robust"); None = no test
     huber: float = None                      # the Huber threshold of the point-to-plane residual, a length; None = plain least squares
     huber_colour: float = None               # the same for the intensity residual, in levels of 255; needs ``colour``
+    pyramid: tuple = None                    # ICP steps per level, finest first (module docstring, "pyramid"); ``iterations`` is then not used.  None = one resolution
+    jump: float = 0.05                       # of the depth pyramid: a block averages the valid depths within (1 + jump) of its nearest; inf = all of them
 
     def __post_init__(self):
+        if self.pyramid is not None:
+            steps = tuple(self.pyramid) if np.ndim(self.pyramid) == 1 else ()
+            if not steps or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) or i < 0 for i in steps) or not any(i > 0 for i in steps):
+                raise ValueError(f"pyramid must be None or the steps per level, integers >= 0 with one > 0, finest first; got {self.pyramid!r}")
+            if len(steps) > int(_lib.load().edv_pyramid_max_levels()):
+                raise ValueError(f"a pyramid has at most {int(_lib.load().edv_pyramid_max_levels())} levels (PYRAMID_MAX_LEVELS), got {len(steps)}")
+            object.__setattr__(self, "pyramid", tuple(int(i) for i in steps))
+        _one_plus_jump(self.jump)
+        object.__setattr__(self, "jump", float(self.jump))
         if self.colour is not None:
             if not _positive(self.colour):
                 raise ValueError(f"colour must be None or finite and positive, got {self.colour!r}")
@@ -701,6 +754,194 @@ def frame_normals(depth, spec: Cloud, output: str = "host"):
         return host.numpy().copy()
 
 
+def _one_plus_jump(jump) -> np.float32:
+    """1 + jump as the float32 both implementations compare with: formed in Python doubles and rounded once."""
+    if isinstance(jump, bool) or not isinstance(jump, (int, float, np.floating, np.integer)) or not jump >= 0.0:
+        raise ValueError(f"jump must be a number >= 0 (inf: every valid depth of a block is used), got {jump!r}")
+    return np.float32(1.0 + float(jump))
+
+
+def _pyramid_sizes(h: int, w: int, levels) -> list:
+    """[(h_l, w_l) for l = 1 .. levels]: each level half the one below, an odd last row or column dropped."""
+    most = int(_lib.load().edv_pyramid_max_levels()) - 1
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= levels <= most:
+        raise ValueError(f"levels must be an integer in 1 .. {most} (PYRAMID_MAX_LEVELS - 1), got {levels!r}")
+    sizes = []
+    for l in range(1, int(levels) + 1):
+        h, w = h // 2, w // 2
+        if h < 1 or w < 1:
+            raise ValueError(f"level {l} of the pyramid holds no pixel")
+        sizes.append((h, w))
+    return sizes
+
+
+def _check_level0(spec: Cloud) -> None:
+    """What the depth pyramid needs of the Cloud: a stored +0 must mean "not valid" at every level."""
+    if int(spec.step) != 1:
+        raise ValueError(f"level 0 of the pyramid is the full-resolution frame: the Cloud must have step 1, got {spec.step}")
+    _, _, gain, near, _ = spec.scalars()
+    if not near >= 0.0 or not gain > 0.0:
+        raise ValueError(f"the pyramid needs near >= 0 and gain > 0 (as float32), got near={spec.near!r}, gain={spec.gain!r}")
+
+
+def _check_pyramid(depth, spec, levels, jump, frame):
+    n, h, w = _check_clip(depth, spec, None)
+    if not 1 <= n <= MAX_FRAMES or h < 1 or w < 1:
+        raise ValueError(f"1 to {MAX_FRAMES} frames that are not empty, got {n} x {h} x {w}")
+    if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
+        raise ValueError(f"frame must be an integer in 0 .. {n - 1}, got {frame!r}")
+    _check_level0(spec)
+    return n, h, w, _pyramid_sizes(h, w, levels), _one_plus_jump(jump), spec.frame_mask(n, h, w)
+
+
+def _check_rgb_pyramid(frames, levels, frame):
+    if frames.ndim != 4 or frames.shape[3] != 3 or str(frames.dtype).replace("torch.", "") != "uint8":
+        raise ValueError(f"expected uint8 frames [n, h, w, 3], got {frames.dtype} {tuple(frames.shape)}")
+    n, h, w = (int(v) for v in frames.shape[:3])
+    if n < 1 or h < 1 or w < 1 or h * w >= 2 ** 31:
+        raise ValueError(f"frames that are not empty and hold fewer than 2^31 pixels each, got {n} x {h} x {w}")
+    if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
+        raise ValueError(f"frame must be an integer in 0 .. {n - 1}, got {frame!r}")
+    return n, h, w, _pyramid_sizes(h, w, levels)
+
+
+def _blocks(a: np.ndarray):
+    """The four pixels of every 2 x 2 block of a [h, w, ...] in block order: (2y, 2x), (2y, 2x+1), (2y+1, 2x), (2y+1, 2x+1)."""
+    h, w = a.shape[0] // 2, a.shape[1] // 2
+    return [a[i:2 * h:2, j:2 * w:2] for i in (0, 1) for j in (0, 1)]
+
+
+def _reduce_depth(d: np.ndarray, one_plus_jump: np.float32) -> np.ndarray:
+    """Level l+1 of the float32 level ``d`` whose +0 means "not valid" (module docstring, "pyramid")."""
+    block = _blocks(d)
+    valid = [b != 0 for b in block]
+    zero, one = np.float32(0.0), np.float32(1.0)
+    with np.errstate(all="ignore"):
+        m = np.full(block[0].shape, np.inf, np.float32)
+        for b, v in zip(block, valid):
+            m = np.where(v, np.minimum(m, b), m)
+        limit = m * one_plus_jump
+        s, c = np.zeros(m.shape, np.float32), np.zeros(m.shape, np.float32)
+        for b, v in zip(block, valid):
+            used = v & (b <= limit)
+            s, c = np.where(used, s + b, s), np.where(used, c + one, c)     # +0 + d == d: the sum starts from the first used value
+        return np.where(c > zero, s / c, zero).astype(np.float32)
+
+
+def depth_pyramid_host(depth, spec: Cloud, levels: int, jump: float = 0.05, frame: int = 0) -> list:
+    """``depth_pyramid`` in numpy, the same operations in the same order: the two agree bit for bit."""
+    depth = np.asarray(depth)
+    n, h, w, sizes, one_plus_jump, mask = _check_pyramid(depth, spec, levels, jump, frame)
+    lo, span, gain, near, far = spec.scalars()
+    x = depth[frame]
+    with np.errstate(all="ignore"):
+        d = x if spec.source == "depth" else np.float32(1.0) / (lo + span * x)
+        z = d * gain
+        keep = (z > near) & (z < far)
+    if mask is not None:
+        keep &= (mask[frame] if mask.ndim == 3 else mask) != 0
+    d = np.where(keep, d, np.float32(0.0)).astype(np.float32)
+    out = []
+    for _ in sizes:
+        d = _reduce_depth(d, one_plus_jump)
+        out.append(d)
+    return out
+
+
+def rgb_pyramid_host(frames, levels: int, frame: int = 0) -> list:
+    """``rgb_pyramid`` in numpy: the two agree in every byte."""
+    frames = np.asarray(frames)
+    n, h, w, sizes = _check_rgb_pyramid(frames, levels, frame)
+    c = frames[frame]
+    out = []
+    for _ in sizes:
+        a = [b.astype(np.uint16) for b in _blocks(c)]
+        c = ((((a[0] + a[1]) + a[2]) + a[3] + np.uint16(2)) >> np.uint16(2)).astype(np.uint8)
+        out.append(c)
+    return out
+
+
+def _pyramid_layout(lib, h: int, w: int, levels: int):
+    """(the pixels of levels 1 .. levels together, the pixels in front of each): ``edv_pyramid_pixels``."""
+    offsets = (C.c_int64 * levels)()
+    total = int(lib.edv_pyramid_pixels(h, w, levels, offsets))
+    if total < 1:
+        raise ValueError(f"no pyramid of {levels} levels over {h} x {w}")
+    return total, [int(o) for o in offsets]
+
+
+def _depth_pyramid_device(lib, sel, frame: int, sizes, one_plus_jump, device):
+    """``edv_depth_pyramid`` of one frame of the selection on the current stream: (the buffer, float32 views [h_l, w_l] of its levels) on the GPU."""
+    total, offsets = _pyramid_layout(lib, int(sel.h), int(sel.w), len(sizes))
+    buf = torch.empty(total, dtype=torch.float32, device=device)
+    _lib.check(lib.edv_depth_pyramid(C.byref(sel), frame, len(sizes), float(one_plus_jump), buf.data_ptr(), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+               "edv_depth_pyramid")
+    return buf, [buf[o:o + h * w].view(h, w) for o, (h, w) in zip(offsets, sizes)]
+
+
+def _rgb_pyramid_device(lib, rgb: torch.Tensor, frame: int, sizes, device):
+    """``edv_rgb_pyramid`` of one frame of the contiguous uint8 tensor [n, h, w, 3] on the current stream: (the buffer, uint8 views [h_l, w_l, 3])."""
+    n, h, w = (int(v) for v in rgb.shape[:3])
+    total, offsets = _pyramid_layout(lib, h, w, len(sizes))
+    buf = torch.empty(3 * total, dtype=torch.uint8, device=device)
+    _lib.check(lib.edv_rgb_pyramid(rgb.data_ptr(), n, h, w, frame, len(sizes), buf.data_ptr(), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "edv_rgb_pyramid")
+    return buf, [buf[3 * o:3 * (o + lh * lw)].view(lh, lw, 3) for o, (lh, lw) in zip(offsets, sizes)]
+
+
+def _levels_out(buf: torch.Tensor, levels: list, output: str, device):
+    """The levels as they are (tensors, ordered on the current stream) or as numpy arrays: one copy of the buffer, for which the host waits."""
+    if output == "device":
+        return levels
+    host = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=True)
+    host.copy_(buf, non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    flat, out, at = host.numpy(), [], 0
+    for l in levels:
+        out.append(flat[at:at + l.numel()].reshape(tuple(l.shape)).copy())
+        at += l.numel()
+    return out
+
+
+def depth_pyramid(depth, spec: Cloud, levels: int, jump: float = 0.05, frame: int = 0, output: str = "host") -> list:
+    """Levels 1 .. ``levels`` of the depth pyramid of frame ``frame`` (module docstring, "pyramid"): a list of float32 [h_l, w_l], the raw depth
+    (the cloud's depth without its gain) averaged over 2 x 2 blocks, the nearest surface of a block alone, +0 where nothing is valid.
+    ``depth`` is float32 [n, h, w], a numpy array or a tensor on the GPU; ``spec`` needs step 1, near >= 0 and gain > 0, its K and pose are not
+    looked at.  One launch (``edv_depth_pyramid``) on the caller's current stream: numpy arrays, complete when returned, or with
+    ``output="device"`` tensors ordered on that stream."""
+    if output not in ("host", "device"):
+        raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+    if isinstance(depth, torch.Tensor):
+        if not depth.is_cuda:
+            raise ValueError("a depth tensor must live on the GPU (pass host data as a numpy array)")
+        device = depth.device
+    else:
+        depth, device = np.asarray(depth), torch.device("cuda", torch.cuda.current_device())
+    n, h, w, sizes, one_plus_jump, mask = _check_pyramid(depth, spec, levels, jump, frame)
+    with torch.cuda.device(device):
+        x = _on_device(depth, device)
+        mask_d = None if mask is None else _staged(mask, device)
+        buf, out = _depth_pyramid_device(_lib.load(), selection(x, spec, mask_d), int(frame), sizes, one_plus_jump, device)
+        return _levels_out(buf, out, output, device)
+
+
+def rgb_pyramid(frames, levels: int, frame: int = 0, output: str = "host") -> list:
+    """Levels 1 .. ``levels`` of the colour pyramid of frame ``frame`` of ``frames`` (uint8 [n, h, w, 3], an array or a tensor on the GPU): a list of
+    uint8 [h_l, w_l, 3], per channel (a + b + c + d + 2) >> 2 over the depth pyramid's blocks.  One launch (``edv_rgb_pyramid``) on the caller's
+    current stream; ``output`` as for ``depth_pyramid``."""
+    if output not in ("host", "device"):
+        raise ValueError(f"output must be 'host' or 'device', got {output!r}")
+    if isinstance(frames, torch.Tensor):
+        if not frames.is_cuda:
+            raise ValueError("a frames tensor must live on the GPU (pass host data as a numpy array)")
+        device = frames.device
+    else:
+        frames, device = np.asarray(frames), torch.device("cuda", torch.cuda.current_device())
+    n, h, w, sizes = _check_rgb_pyramid(frames, levels, frame)
+    with torch.cuda.device(device):
+        buf, out = _rgb_pyramid_device(_lib.load(), _on_device(frames, device), int(frame), sizes, device)
+        return _levels_out(buf, out, output, device)
+
+
 def _check_robust(colour: bool, min_cos=None, huber=None, huber_colour=None):
     """(min_cos or None, huber, huber_colour) of checked options of the robust sums; a threshold that is not given is +inf."""
     if min_cos is not None and (not _number(min_cos) or not -1.0 <= min_cos <= 1.0):
@@ -828,6 +1069,17 @@ class _IcpHost:
     def sums(self, live: np.ndarray) -> np.ndarray:
         return _ordered_sum(self.terms(live))
 
+    @staticmethod
+    def placed(depth, frames):
+        """The clip and its frames where the sums read them: here, as they are."""
+        return depth, frames
+
+    @staticmethod
+    def pyramid(depth, spec, frame, levels, jump, frames):
+        """(the depth levels 1 .. ``levels`` of the frame as clips [1, h_l, w_l], its colour levels [1, h_l, w_l, 3] or None without ``frames``)."""
+        return ([d[None] for d in depth_pyramid_host(depth, spec, levels, jump, frame)],
+                None if frames is None else [c[None] for c in rgb_pyramid_host(frames, levels, frame)])
+
 
 class _IcpDevice:
     """The same on the GPU (``edv_icp_sums``, or ``edv_icp_scaled_sums`` with ``scale``): the clip, the mask, the model and the workspace are
@@ -903,6 +1155,18 @@ class _IcpDevice:
             self.sums_h.copy_(self.sums_d, non_blocking=True)
             stream.synchronize()
             return self.sums_h.numpy().copy()
+
+    @staticmethod
+    def placed(depth, frames):
+        """The clip and its frames on the GPU, once: host arrays go to the current device, or to the depth tensor's; tensors stay as they are."""
+        device = depth.device if isinstance(depth, torch.Tensor) and depth.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return _on_device(depth, device), None if frames is None else _on_device(frames, device)
+
+    @staticmethod
+    def pyramid(depth, spec, frame, levels, jump, frames):
+        """The same on the GPU (``edv_depth_pyramid``, ``edv_rgb_pyramid``: a launch each, no host wait): the levels are tensors and stay there."""
+        return ([d[None] for d in depth_pyramid(depth, spec, levels, jump, frame, output="device")],
+                None if frames is None else [c[None] for c in rgb_pyramid(frames, levels, frame, output="device")])
 
 
 def _estimate(ctx, spec: Cloud, frame: int) -> np.ndarray:
@@ -1010,6 +1274,16 @@ def apply_twist(T, xi) -> np.ndarray:
     return T
 
 
+def _pyramid_plan(track, spec: Cloud, h: int, w: int) -> list:
+    """[(level, steps)] of the levels that are run, the coarsest first (module docstring, "pyramid"); without a pyramid [(0, iterations)]."""
+    if track.pyramid is None:
+        return [(0, track.iterations)]
+    _check_level0(spec)
+    if len(track.pyramid) > 1:
+        _pyramid_sizes(h, w, len(track.pyramid) - 1)                     # every level holds a pixel, also one that is not run
+    return [(level, steps) for level, steps in reversed(list(enumerate(track.pyramid))) if steps > 0]
+
+
 def _track(tsdf, context, depth, spec, track, frame, frames=None):
     """``Tsdf.track`` and ``TsdfHost.track``: everything but the sums is this host code."""
     if not isinstance(track, Track):
@@ -1022,28 +1296,41 @@ def _track(tsdf, context, depth, spec, track, frame, frames=None):
     if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < n:
         raise ValueError(f"frame must be an integer in 0 .. {n - 1}, got {frame!r}")
     guess = _pose4(spec.pose[frame if spec.pose.shape[0] > 1 else 0])
-    views = track.views(spec.K[frame if spec.K.shape[0] > 1 else 0], guess, (h, w))
-    model = tsdf.raycast(views, min_weight=track.min_weight, normals=True, output=context.output)
+    K = spec.K[frame if spec.K.shape[0] > 1 else 0]
+    plan = _pyramid_plan(track, spec, h, w)                              # (level, steps), the coarsest level first; one resolution: [(0, iterations)]
+    coarse = coarse_rgb = None
+    if plan[0][0]:                                                       # the clip placed once for the pyramids and level 0; the levels once a frame, with the gain of the guess
+        depth, frames = context.placed(depth, frames)
+        coarse, coarse_rgb = context.pyramid(depth, spec, frame, plan[0][0], track.jump, frames)
     max_dist = tsdf.volume.trunc if track.max_dist is None else track.max_dist
-    ctx = context(depth, spec, model, views, max_dist, frame, scale=track.scale, frames=frames, robust=track.robust() or None)   # the live normals: once, here
     T, pairs, rms, sigma = guess.copy(), 0, float("nan"), 1.0
     lost = (guess, 1.0) if track.scale else (guess,)
-    for _ in range(track.iterations):
-        if track.scale:
-            ctx.set_gain(np.float32(float(spec.gain) * sigma))
-        sums = ctx.sums(_live_cam(ctx.kinv, T))
-        if frames is not None:
-            sums = _with_colour(sums, track.colour)
-        pairs = int(sums[-1])
-        rms = math.sqrt(sums[-2] / sums[-1]) if sums[-1] > 0.0 else float("nan")
-        xi = icp_solve(sums, track.min_pairs)
-        if xi is None:
-            return lost[0], pairs, rms, True, *lost[1:]
-        T = apply_twist(T, xi[:6])
-        if track.scale:
-            sigma = sigma * (1.0 + float(xi[6]))
-            if not (math.isfinite(sigma) and sigma > 0.0 and 1.0 / (1.0 + track.max_scale_step) <= sigma <= 1.0 + track.max_scale_step):
+    for level, steps in plan:
+        if level == 0:
+            clip, one, at, rgb, Kl = depth, spec, frame, frames, K
+        else:                                                            # the stored level is an ordinary clip; the gain was kept out of it
+            clip, at, rgb = coarse[level - 1], 0, None if frames is None else coarse_rgb[level - 1]
+            Kl = K * np.array([[0.5 ** level], [0.5 ** level], [1.0]])  # exact: a power of two
+            one = Cloud(K=Kl, pose=T, source="depth", gain=spec.gain, near=spec.near, far=spec.far)
+        views = track.views(Kl, T, tuple(int(v) for v in clip.shape[1:3]))   # the model: cast from the current estimate, the guess for the first level
+        model = tsdf.raycast(views, min_weight=track.min_weight, normals=True, output=context.output)
+        ctx = context(clip, one, model, views, max_dist, at, scale=track.scale, frames=rgb, robust=track.robust() or None)   # the live normals: once a level, here
+        for _ in range(steps):
+            if track.scale:
+                ctx.set_gain(np.float32(float(spec.gain) * sigma))
+            sums = ctx.sums(_live_cam(ctx.kinv, T))
+            if frames is not None:
+                sums = _with_colour(sums, track.colour)
+            pairs = int(sums[-1])
+            rms = math.sqrt(sums[-2] / sums[-1]) if sums[-1] > 0.0 else float("nan")
+            xi = icp_solve(sums, track.min_pairs)
+            if xi is None:
                 return lost[0], pairs, rms, True, *lost[1:]
+            T = apply_twist(T, xi[:6])
+            if track.scale:
+                sigma = sigma * (1.0 + float(xi[6]))
+                if not (math.isfinite(sigma) and sigma > 0.0 and 1.0 / (1.0 + track.max_scale_step) <= sigma <= 1.0 + track.max_scale_step):
+                    return lost[0], pairs, rms, True, *lost[1:]
     U, _, Vt = np.linalg.svd(T[:3, :3])
     T[:3, :3] = U @ Vt
     return (T, pairs, rms, False, sigma) if track.scale else (T, pairs, rms, False)
@@ -1058,6 +1345,7 @@ def _track_clip(tsdf, depth, spec, track, frames):
         raise ValueError("Track(colour=...) compares colours: it takes a coloured volume and the clip's frames")
     if spec.pose.shape[0] != 1:
         raise ValueError(f"tracking starts from one pose, the first camera's; the Cloud holds {spec.pose.shape[0]}")
+    _pyramid_plan(track, spec, h, w)                                     # a pyramid the clip cannot have is refused before frame 0 is integrated
     out = Tracked(np.zeros((n, 4, 4)), np.zeros(n, np.int64), np.zeros(n), np.zeros(n, bool), np.ones(n) if track.scale else None)
     T, sigma = _pose4(spec.pose[0]), 1.0
     for i in range(n):
@@ -1490,7 +1778,9 @@ class Tsdf:
         guess.  With ``track.scale`` the system is 7 x 7 and the tuple ends with the scale factor found, a Python float relative to
         ``spec.gain``, 1.0 for a lost frame.  With ``track.colour`` the volume must be coloured and ``frames`` (uint8 [n, h, w, 3], as for
         ``integrate``) given: every pair also compares the frame's intensity with the model's (module docstring, "colour"); otherwise ``frames``
-        is not looked at.  On the caller's current stream; the host waits once per step."""
+        is not looked at.  With ``track.pyramid`` the steps run coarse to fine (module docstring, "pyramid"): the frame's depth and colour levels
+        are formed once (a launch each) and stay on the GPU, every level that is run ray-casts the volume at its own size from the current
+        estimate, and ``iterations`` is not used.  On the caller's current stream; the host waits once per step."""
         with torch.cuda.device(self.device):
             return _track(self, _IcpDevice, self._own(depth), spec, track, frame, frames)
 

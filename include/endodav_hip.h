@@ -682,6 +682,42 @@ int edv_icp_robust_sums(const edv_cloud_selection *sel, int64_t frame, const uin
                         int32_t cols, const float *live_normals_dev, double min_cos, double huber, double huber_colour, double *sums_dev, void *workspace_dev,
                         size_t workspace_bytes, void *stream);
 
+/* ---- coarse-to-fine tracking: depth and colour pyramids of the live frame (fusion.Track(pyramid=..., jump=...), fusion.depth_pyramid, fusion.rgb_pyramid) ----
+ * Additive entry points: the ABI version stays as it is.  The steps above run at one resolution.  With a pyramid the tracker runs its first steps
+ * on coarse copies of the live frame against the volume ray-cast at the same coarse size: a step at half size works on a quarter of the
+ * pixels, and the same motion is a smaller displacement in large pixels.  The sums, the normals and the ray-cast take any grid size and any
+ * intrinsics, so the device work that is new is what makes the levels.  fusion.depth_pyramid_host and fusion.rgb_pyramid_host are the numpy
+ * mirrors, bit for bit.
+ * Levels: level 0 is the frame, h_0 x w_0.  Level l+1 is (h_l / 2) x (w_l / 2), the division rounded down: an odd last row or column is
+ *   dropped.  Every level must hold a pixel.  edv_pyramid_max_levels(): 6, level 0 included, so 1 <= levels <= 5 coarser levels a call.
+ *   Pixel (y, x) of level l+1 is made from the block (2y, 2x), (2y, 2x+1), (2y+1, 2x), (2y+1, 2x+1) of level l, in that order.  With pixel
+ *   centres at x + 0.5 the camera of level l is K_l = diag(2^-l, 2^-l, 1) K, exactly.
+ * edv_depth_pyramid: the selection is the cloud's with step == 1, near_z >= 0 and gain > 0; frame is one frame of it.  All of it fp32, every
+ *   operation rounded on its own:
+ *     level 0   d = x (mode 0), or d = 1 / (lo + span*x) (mode 1): the selection's depth rule without its last multiply by gain.  The pixel is
+ *               valid when the selection keeps it: mask != 0 and near_z < d*gain < far_z (NaN and Inf fail).  A valid d is > 0.
+ *     level >=1 a pixel is valid when its stored value is not 0.
+ *     reduce    m = the smallest valid value of the block;  a valid value is used when d <= m * one_plus_jump;  s = the used values added in
+ *               block order, starting from the first used one;  c = their number;  the stored value is s / (float)c, or +0 where nothing is
+ *               valid.  The nearest surface wins: a block across a depth edge is not smeared.  one_plus_jump = +inf uses every valid value,
+ *               1 only those equal to m.
+ *   The gain stays out of the stored values: a level is an ordinary mode-0 clip for the calls above with the gain of level 0, z = d * gain,
+ *   and their near_z < z test drops the zeros.
+ * edv_rgb_pyramid: frames_dev uint8 [n][h][w][3], frame one of them; per channel (a + b + c + d + 2) >> 2 over the same block, in integers.
+ * The output of either call: levels 1 .. levels one behind the other, tightly, each row-major: level l starts offsets[l-1] pixels into the
+ *   buffer, 4 bytes a pixel for depth and 3 for colour.  edv_pyramid_pixels returns the pixels of all levels together and, where offsets_host
+ *   is not NULL, writes offsets_host[0 .. levels-1]; it returns 0, and writes nothing, for a shape the calls refuse.
+ * One launch a call, all levels: a workgroup of 256 owns a 32 x 32 tile of level 0 (32 = 2^5: the tile holds whole blocks of every level),
+ *   reads its pixels of level 0 once, stores level 1 and reduces on through LDS.  No atomics, no waiting between workgroups; every pixel of
+ *   every level is written exactly once, zeros included, and nothing else is: the buffer needs no clearing and the same input gives the same bits.
+ * A null pointer, a selection the cloud refuses or with step != 1, near_z < 0 or gain <= 0 (or NaN), frame outside the clip, one_plus_jump
+ * below 1 or NaN, levels outside 1 .. 5, a level without a pixel, h*w >= 2^31 and a depth output that is not 4-byte aligned return non-zero and
+ * launch nothing. */
+int32_t edv_pyramid_max_levels(void);
+size_t edv_pyramid_pixels(int32_t h, int32_t w, int32_t levels, int64_t *offsets_host);
+int edv_depth_pyramid(const edv_cloud_selection *sel, int64_t frame, int32_t levels, float one_plus_jump, float *levels_dev, void *stream);
+int edv_rgb_pyramid(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, int64_t frame, int32_t levels, uint8_t *levels_dev, void *stream);
+
 /* ---- whole-video stitching on the device (infer_video_depth(stitch="device"); endodav.py:213-254, utils/util.py:40-74) ----
  * disp_dev: one window's network-size disparity [32, ih, iw].  Both calls upsample it to the frame size [fh, fw] on the fly (bilinear,
  * align_corners=True, bit-identical to edv_bilinear), so the 32 frame-size maps are never materialised.
